@@ -31,6 +31,19 @@ script; the multi-GPU and volume problems use the closed forms (documented in th
 
 Counts: exactly --warmup untimed and --steps timed iterations (odd counts allowed).
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does what the headline needs and no more:
+it builds the problem, warms up, times the K iterations and prints the line (`value`,
+`ms_per_step`, the loop-time roofline).  Everything else described above -- the CPU baseline, the
+single-GPU 2-D legs, the volume legs, the isolated per-kernel timings and, at N > 1, the
+communication probes and the strong-scaling entry -- runs after the headline only with `--full`
+(their keys are absent or null in a plain line).
+
+`--dump-outputs DIR` writes what the last timed iteration computed as DIR/x.npy, DIR/z.npy (the
+primal and dual iterates, in the run's dtype) and DIR/diagnostics.npy (that iteration's two
+relative-improvement norms, fp64); at N > 1 every rank writes its own rows as <name>_rank<r>.npy.
+Outputs larger than 48 MiB in all are cut to a fixed seeded sample of their elements.  The
+inputs are seeded, so two runs with the same arguments are compared file for file.
+
 Prints ONE JSON line on rank 0.
 """
 
@@ -48,6 +61,9 @@ import torch.distributed as dist
 METRIC = 'PDS iters/sec on 4096² TV-deconv; achieved HBM GB/s vs roofline at 1/2/4/8 GPU'
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md)
 TRAFFIC_JSON = 'profiles/r6_profc3_traffic.json'  # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of the step kernel (tools/prof_nm.sh r6_profc3)
+DUMP_BUDGET = 48 << 20  # --dump-outputs: bytes of array data in all (larger outputs are sampled)
+DUMP_WHOLE = 64 << 10  # arrays up to this many bytes are never sampled
+DUMP_SEED = 20240607  # seed of the sample's indices
 
 
 def phantom(shape, n_rect, seed):
@@ -346,18 +362,46 @@ def spin_up_fixed(eng, min_ms=200.0):
         busy += e0.elapsed_time(e1)
 
 
-def fused_2d(pds, dtype, K, W, chunk=32):
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET):
+    """--dump-outputs: write each of `arrays` (name -> tensor or ndarray, fp32 or fp64 as computed) as
+    DIR/<name>.npy.  When they hold more than `budget` bytes together, every array above DUMP_WHOLE
+    bytes is cut in proportion to a fixed sample of its flattened elements: indices drawn with a fixed
+    seed, sorted, the same in every run with the same shapes, so two builds are compared element for
+    element."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: torch.as_tensor(v).reshape(-1) for k, v in arrays.items()}
+    nbytes = {k: t.numel() * t.element_size() for k, t in arrays.items()}
+    total = sum(nbytes.values())
+    small = sum(b for b in nbytes.values() if b <= DUMP_WHOLE)  # short arrays (the diagnostics) stay whole
+    for i, (name, t) in enumerate(arrays.items()):
+        if total > budget and nbytes[name] > DUMP_WHOLE:
+            m = max(1, int(t.numel() * ((budget - small) / (total - small))))
+            idx = np.sort(np.random.default_rng([DUMP_SEED, i]).integers(0, t.numel(), m))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, f'{name}.npy'), t.cpu().numpy())
+
+
+def fused_2d(pds, dtype, K, W, chunk=32, kernels=True, outputs=False):
     """Exactly W untimed then K timed iterations of a fused 2-D problem (PDS2DEngine, fixed
     count); HIP events on the launch stream bracket the K iterations.  Returns ms per
-    iteration, the isolated per-kernel launch means and the engine facts."""
+    iteration, the engine facts and, with `kernels`, the isolated per-kernel launch medians (a run
+    of their own after the timed region); with `outputs`, copies of what the last timed iteration
+    left (x, z and its row of the convergence diagnostics) under 'outputs'."""
     from pycsou_amd import _ops as O
     from pycsou_amd.opt.engine import engine_class
     spec = pds._fused_spec()
     assert spec is not None, 'problem must take the fused 2-D engine'
     eng = engine_class(spec)(spec, dtype, pds.tau, pds.sigma, pds.rho, O.to_dev(pds.x0, dtype), O.to_dev(pds.z0, dtype))
     total = W + K + 4
+    state = [b for b in (eng.X, eng.Z, getattr(eng, 'ZM', None)) if b is not None]
+    init = [b[0].clone() for b in state]
     eng.prepare_fixed(max(total, 4000), chunk)
     spin_up_fixed(eng)
+    # the spin-up iterates for a time, not a count: back to the initial iterate, so the W + K
+    # iterations below compute the same thing in every run
+    for b, b0 in zip(state, init):
+        b[0].copy_(b0)
+    del init
     eng.prepare_fixed(total, chunk)  # fresh loop state: exactly W + K iterations below
     eng.advance_fixed(W)
     torch.cuda.synchronize()
@@ -369,11 +413,16 @@ def fused_2d(pds, dtype, K, W, chunk=32):
     ms = t0.elapsed_time(t1) / K
     it_done = int(eng.ctrl.view(torch.int32)[0].item())
     assert it_done == W + K, (it_done, W, K)  # every timed launch really iterated
+    out = None
+    if outputs:
+        p = eng._fixed_p  # the buffers the last timed iteration wrote
+        out = {'x': eng.X[p].clone(), 'z': eng.Z[p].clone(),
+               'diagnostics': eng.hist[2 * (it_done - 1):2 * it_done].clone()}
     # per-kernel means: an event pair around each launch of 100 eager iterations (after the
     # timed region; the rocprofv3 kernel-trace averages in profiles/ must agree)
-    kern = eng.time_iteration_kernels(min(max(K, 20), 100))
+    kern = eng.time_iteration_kernels(min(max(K, 20), 100)) if kernels else None
     res = {'ms_per_step': ms, 'kernels_ms': kern, 'nblocks': eng.nblocks, 'native': eng.native,
-           'fkind': int(eng.fkind), 'nmarch': getattr(eng, 'cty', None) is not None}
+           'fkind': int(eng.fkind), 'nmarch': getattr(eng, 'cty', None) is not None, 'outputs': out}
     del eng
     torch.cuda.empty_cache()
     return res
@@ -706,9 +755,11 @@ def depth_trial(pds, comm, eng1, depths, W, K):
     return best, trials
 
 
-def slab_bench(n, dtype, K, W, world):
+def slab_bench(n, dtype, K, W, world, full=True, outputs=False):
     """Weak scaling: a (n world) x n image, one n x n row slab per rank; K timed iterations
-    (barrier + synchronize on both sides; the caller takes the max over ranks)."""
+    (barrier + synchronize on both sides; the caller takes the max over ranks).  `full`: after the
+    timed region also the communication probe and the isolated step timing; `outputs`: this rank's
+    rows of x and z and the diagnostics row of the last timed iteration under 'outputs'."""
     from pycsou_amd.parallel import DistComm, SlabPDS2D
     from pycsou_amd.parallel.slab import comm_probe
     pds = build_problem(n * world, n, dtype, lipschitz='analytic')
@@ -743,6 +794,12 @@ def slab_bench(n, dtype, K, W, world):
         eng.init_loop(total, total, -1.0)
         eng.advance(8)
         torch.cuda.synchronize()
+    # the spin-up and the trials iterated for a time, not a count: back to the initial iterate
+    # (x0 = z0 = 0, halos and padding included), so the W + K iterations below compute the same
+    # thing in every run
+    torch.cuda.synchronize()
+    for b in eng.X + eng.Z:
+        b.zero_()
     eng.init_loop(total, total, -1.0)  # fixed count: the loop never stops early
     eng.advance(W)
     torch.cuda.synchronize()
@@ -762,8 +819,12 @@ def slab_bench(n, dtype, K, W, world):
         t = torch.tensor([dt], dtype=torch.float64, device='cuda' if dist.get_backend() == 'nccl' else 'cpu')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    probe = comm_probe(eng) if world > 1 else None  # compute / all-gather / exchange timed apart
-    kern_ms = eng.time_step_kernel(min(K, 100))  # a step here also holds the sums all-gather + halos
+    out = None
+    if outputs:
+        _, x, z, h = eng.result()
+        out = {'x': x, 'z': z, 'diagnostics': h[-1]}
+    probe = comm_probe(eng) if world > 1 and full else None  # compute / all-gather / exchange timed apart
+    kern_ms = eng.time_step_kernel(min(K, 100)) if full else None  # a step here also holds the sums all-gather + halos
     if eng.depth > 1:
         loop = f'native deep-halo, depth {eng.depth} (pcs_slab2d_deep_run)'
     else:
@@ -771,7 +832,7 @@ def slab_bench(n, dtype, K, W, world):
             'python (gloo rehearsal)' if world > 1 and dist.get_backend() != 'nccl' else 'python')
     return {'ms_per_step': dt * 1e3 / K, 'kernel_ms': kern_ms, 'kernel_ms_isolated': kern_ms, 'nblocks': eng.nblocks,
             'loop': loop, 'loop_fallback': fallback, 'schedule_trial_ms': getattr(eng, 'tune_ms', None),
-            'depth': eng.depth, 'depth_trial_ms_per_iter': trials, 'comm': probe}
+            'depth': eng.depth, 'depth_trial_ms_per_iter': trials, 'comm': probe, 'outputs': out}
 
 
 def strong_bench(n, dtype, K, W, world, depths=(1, 2, 4, 8)):
@@ -915,13 +976,20 @@ def main():
     ap.add_argument('--warmup', type=int, default=50)
     ap.add_argument('--size', type=int, default=4096)
     ap.add_argument('--dtype', default='f32', choices=['f32', 'f64'])
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline: the CPU baseline, the 2-D legs, the volume legs, the isolated per-kernel '
+                         'timings and (N > 1) the communication probes and the strong-scaling entry; without it the '
+                         'run sets up, warms up, times --steps iterations and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last of them computed (x, z, its diagnostics row) as '
+                         'DIR/<name>.npy; outputs above 48 MiB in all are cut to a fixed seeded sample')
     ap.add_argument('--cpu-iters', type=int, default=3)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--volumes', default='c4:512:f32:20,c5:1024:f64:20,c4_cen:512:f32:20:centered,c5_cen:1024:f64:20:centered',
-                    help='volume legs name:edge:dtype:steps[:kind], comma separated ("" skips them)')
+                    help='--full: volume legs name:edge:dtype:steps[:kind], comma separated ("" skips them)')
     ap.add_argument('--volume-timeout', type=float, default=240.0)
     ap.add_argument('--legs', default='c2,c3_nonsep,c2_lap,c2_cen,c3_cen,c3_f64,c3_cen_f64,conv63,cps_inpaint',
-                    help='single-GPU 2-D legs after the headline: c2 (2048^2 denoising), c3_nonsep (non-separable '
+                    help='--full: single-GPU 2-D legs after the headline: c2 (2048^2 denoising), c3_nonsep (non-separable '
                          'PSF), c2_lap / c2_cen (Laplacian / centered-Gradient K), c3_cen (C3 with the default '
                          'centered Gradient), conv63 (63x63 FFT Convolve2D), cps_inpaint (generic path); "" skips them')
     ap.add_argument('--lipschitz', default='lanczos', choices=['lanczos', 'analytic'],
@@ -967,11 +1035,15 @@ def main():
         # the first multi-rank RCCL run must not lose the line: a stall prints it with an error
         timer = headline_watchdog(args, rank, world, dtype)
         try:
-            res = slab_bench(n, dtype, K, W, world)
+            res = slab_bench(n, dtype, K, W, world, full=args.full, outputs=args.dump_outputs is not None)
         finally:
             timer.cancel()
         res['kernel_ms_isolated'] = res['kernel_ms']
-        res['step_ms_loop'] = res['kernel_ms']
+        # --full: the isolated slab steps' mean; a plain run has only the timed loop itself
+        res['step_ms_loop'] = res['kernel_ms'] if args.full else res['ms_per_step']
+        if res['outputs'] is not None:  # every rank writes the rows of its own slab
+            sfx = f'_rank{rank}' if world > 1 else ''
+            dump_outputs(args.dump_outputs, {k + sfx: v for k, v in res.pop('outputs').items()}, DUMP_BUDGET // world)
     else:
         t0 = time.perf_counter()
         pds = build_problem(n, n, dtype, lipschitz=args.lipschitz)
@@ -979,13 +1051,15 @@ def main():
         lips = {'K': pds.K.lipschitz_cst, 'Conv': pds.F.map2.lipschitz_cst}
         spec = pds._fused_spec()
         assert spec is not None and spec['fkind'] == 2, 'C3 problem must take the fused separable engine'
-        res = fused_2d(pds, dtype, K, W)
+        res = fused_2d(pds, dtype, K, W, kernels=args.full, outputs=args.dump_outputs is not None)
         del pds
+        if res['outputs'] is not None:
+            dump_outputs(args.dump_outputs, res.pop('outputs'))
         # one kernel per iteration, launched back to back from C: the step kernel's duration is
         # the timed region's HIP-event time / K (inter-launch gaps included, so it never exceeds
-        # ms_per_step); the median of isolated event pairs is reported beside it
+        # ms_per_step); with --full the median of isolated event pairs is reported beside it
         res['step_ms_loop'] = res['ms_per_step']
-        res['kernel_ms_isolated'] = res['kernels_ms']['step']
+        res['kernel_ms_isolated'] = res['kernels_ms']['step'] if args.full else None
         res['lipschitz'] = lips
         res['setup_s'] = round(setup, 2)
 
@@ -1033,8 +1107,9 @@ def main():
                                                  '`achieved`)'
                                                  if world == 1 and args.engine != 'slab' else
                                                  'mean of HIP-event pairs around isolated slab steps'),
-                         'kernel_ms': round(res['kernel_ms_isolated'], 5),
-                         'kernel_ms_source': 'median of HIP-event pairs around isolated launches (rounds 1-3 meaning)',
+                         'kernel_ms': round(res['kernel_ms_isolated'], 5) if args.full else None,
+                         'kernel_ms_source': 'median of HIP-event pairs around isolated launches (rounds 1-3 meaning; '
+                                             'a run of its own: --full only)',
                          'alg_bytes_per_launch': alg_bytes,
                          # the 15x15 PSF work beside the bandwidth figure -- per pixel the
                          # normal operator's two 29-tap passes (nmarch) or the four 15-tap separable
@@ -1048,11 +1123,12 @@ def main():
             out['loop'] = res['loop']
             out['loop_fallback'] = res['loop_fallback']
             out['comm'] = res.get('comm')  # compute / all-gather / exchange ms, halo GB/s per side
-        if world == 1 and not args.no_cpu_baseline:
+        out['full'] = args.full
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(n, args.cpu_iters)
         else:
             out['cpu_baseline'] = None
-        if world == 1 and args.engine != 'slab':
+        if args.full and world == 1 and args.engine != 'slab':
             for leg in filter(None, args.legs.split(',')):
                 fn = {'c2': leg_c2, 'c3_nonsep': leg_c3_nonsep, 'c2_lap': leg_c2_lap, 'c2_cen': leg_c2_cen,
                       'c3_cen': leg_c3_cen, 'c3_f64': leg_c3_f64, 'c3_cen_f64': leg_c3_cen_f64, 'conv63': leg_conv63,
@@ -1062,12 +1138,12 @@ def main():
                 except Exception as e:  # noqa: BLE001 -- the C3 line stands on its own
                     out[leg] = {'error': f'{type(e).__name__}: {e}'[:300]}
                     print(f'bench: leg {leg} failed: {out[leg]["error"]}', file=sys.stderr)
-    for leg in filter(None, args.volumes.split(',')):
+    for leg in filter(None, args.volumes.split(',') if args.full else ()):
         name, edge, vdt, vsteps, *vk = leg.split(':')
         out = volume_leg(args, out if rank == 0 else None, f'volume_{name}', int(edge),
                          torch.float64 if vdt == 'f64' else torch.float32, int(vsteps), world, rank,
                          vk[0] if vk else 'forward')
-    if world > 1 and args.strong:
+    if world > 1 and args.strong and args.full:
         # the metric as written: one 4096^2 image over the N ranks (strong scaling), beside the weak headline
         try:
             sres = strong_bench(args.size, dtype, K, W, world)

@@ -6,7 +6,7 @@ out=gpurun_out/${OUT:-r5_c4ab}
 mkdir -p $out
 for cfg in "$@"; do
   envs=""; [ "$cfg" != "-" ] && envs="$cfg"
-  env $envs timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --legs "" \
+  env $envs timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --legs "" \
       --volumes ${VOLS:-c4:512:f32:20,c4_cen:512:f32:20:centered} --no-cpu-baseline > $out/run.json 2> $out/run.err \
       || { echo "FAILED $cfg"; tail -5 $out/run.err; exit 1; }
   python -c "

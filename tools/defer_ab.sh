@@ -6,7 +6,7 @@ out=gpurun_out/${OUT:-r5_defer}
 mkdir -p $out
 for v in "$@"; do
   PCS_DEFER_FIN=$v PCS_N=2048 timeout -k 10 120 python3 tools/sm_probe.py 2>>$out/err.txt | sed "s|^|defer=$v |" | tee -a $out/ab.txt || exit 1
-  PCS_DEFER_FIN=$v timeout -k 10 400 python -u bench.py --steps 300 --warmup 30 --legs ${LEGS:-c2,c2_lap,cps_inpaint,c3_cen,c3_f64} \
+  PCS_DEFER_FIN=$v timeout -k 10 400 python -u bench.py --full --steps 300 --warmup 30 --legs ${LEGS:-c2,c2_lap,cps_inpaint,c3_cen,c3_f64} \
       --volumes "" --no-cpu-baseline > $out/run_$v.json 2>> $out/err.txt || exit 2
   python -c "
 import json; d=json.load(open('$out/run_$v.json'))

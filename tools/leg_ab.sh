@@ -7,7 +7,7 @@ legs=${LEGS:-c3_nonsep}
 mkdir -p $out
 for cfg in "$@"; do
   envs=""; [ "$cfg" != "-" ] && envs="$cfg"
-  env $envs timeout -k 10 300 python -u bench.py --steps ${STEPS:-200} --warmup 20 --legs $legs --volumes "" \
+  env $envs timeout -k 10 300 python -u bench.py --full --steps ${STEPS:-200} --warmup 20 --legs $legs --volumes "" \
       --no-cpu-baseline > $out/run.json 2> $out/run.err || { echo "FAILED $cfg"; tail -5 $out/run.err; exit 1; }
   python -c "
 import json; d=json.load(open('$out/run.json'))

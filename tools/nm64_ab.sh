@@ -6,7 +6,7 @@ out=gpurun_out/${OUT:-r5_nm64ab}
 mkdir -p $out
 for cfg in "$@"; do
   envs=""; [ "$cfg" != "-" ] && envs="$cfg"
-  env $envs timeout -k 10 300 python -u bench.py --steps 200 --warmup 20 --legs c3_f64,c3_cen_f64 --volumes "" \
+  env $envs timeout -k 10 300 python -u bench.py --full --steps 200 --warmup 20 --legs c3_f64,c3_cen_f64 --volumes "" \
       --no-cpu-baseline > $out/run.json 2> $out/run.err || { echo "FAILED $cfg"; tail -5 $out/run.err; exit 1; }
   python -c "
 import json; d=json.load(open('$out/run.json'))

@@ -7,7 +7,7 @@ out=gpurun_out/$1
 mkdir -p $out
 for r in 1 2; do
   for v in 1 0; do
-    PCS_NX_SUB=$v timeout -k 10 200 python bench.py --steps 100 --warmup 10 --legs c3_f64,c3_cen_f64 --volumes "" --no-cpu-baseline 2>/dev/null \
+    PCS_NX_SUB=$v timeout -k 10 200 python bench.py --full --steps 100 --warmup 10 --legs c3_f64,c3_cen_f64 --volumes "" --no-cpu-baseline 2>/dev/null \
       | python3 -c "import json,sys; d=json.loads(sys.stdin.read().splitlines()[-1]); print('nx_sub=$v rep $r', {k: (d[k]['it_per_s'], d[k]['kernels_ms'], d[k]['roofline']['frac']) for k in ('c3_f64','c3_cen_f64')})" >> $out/nxsub_ab.txt || exit 1
   done
 done

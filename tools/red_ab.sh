@@ -7,7 +7,7 @@ mkdir -p $out
 for v in "$@"; do
   if [ "$v" = default ]; then E=PCS_X=0; else E=PCS_LIB_PATH=pycsou_amd/lib/var/$v/libpycsou_hip.so; fi
   env $E PCS_N=2048 timeout -k 10 120 python3 tools/sm_probe.py 2>>$out/err.txt | sed "s|^|$v |" | tee -a $out/ab.txt || exit 1
-  env $E timeout -k 10 300 python -u bench.py --steps 300 --warmup 30 --legs c2,cps_inpaint --volumes "" --no-cpu-baseline \
+  env $E timeout -k 10 300 python -u bench.py --full --steps 300 --warmup 30 --legs c2,cps_inpaint --volumes "" --no-cpu-baseline \
       > $out/run.json 2>> $out/err.txt || exit 2
   python -c "
 import json; d=json.load(open('$out/run.json'))

@@ -8,7 +8,7 @@ for spec in "$@"; do
   var=${spec%%=*}; rest=${spec#*=}; vals=${rest%%:*}; legs=${rest#*:}
   for v in ${vals//,/ }; do
     if [ "$v" = def ]; then E=PCS_X=0; else E=$var=$v; fi
-    env $E timeout -k 10 300 python -u bench.py --steps 300 --warmup 30 --legs $legs --volumes "" --no-cpu-baseline \
+    env $E timeout -k 10 300 python -u bench.py --full --steps 300 --warmup 30 --legs $legs --volumes "" --no-cpu-baseline \
         > $out/run.json 2>> $out/err.txt || exit 2
     python -c "
 import json; d=json.load(open('$out/run.json'))
