@@ -360,6 +360,22 @@ int pcs_pds2d_step_bands(const pcs_pds2d_args* a, int64_t ra0, int64_t rb0, int6
  * pcs_pds_finalize_pending once the run is done, before reading ctrl or hist, and (2) select the
  * result by the parity of Ctrl.it (iterations done: even -> x, z; odd -> xn, zn), not by n. */
 int pcs_pds2d_run(const pcs_pds2d_args* a, int64_t n, hipStream_t stream);
+/* The band-paired schedule of pcs_pds2d_run (deferred finalization only).  A whole image whose seven
+ * step arrays exceed the Infinity Cache runs every iteration as two row-band launches T = [0, m) and
+ * B = [m, rows), T first in even iterations and B first in odd ones, so that every second band launch
+ * rereads the previous iteration's output of its own band on-die.  x, z and the iteration count are
+ * those of the single launch bit for bit; the partials of an iteration are T's tasks then B's, reduced
+ * in that order by the first band launch of the next iteration, so the diagnostics are reproducible and
+ * differ from the single launch's only in the fp64 summation order.  Off unless PCS_RUN_BANDS asks for
+ * it (on the C3 step it measured slower than the single launch): 1 pairs any problem that
+ * pcs_pds2d_step_bands takes, auto pairs where the size rule of csrc/pds.hip says so, 0 or unset keeps
+ * the single launch.  `mode`: -1 = as pcs_pds2d_run will decide, 0 / 1 / 2 = as if PCS_RUN_BANDS were
+ * 0 / 1 / auto.
+ * pcs_pds2d_run_nblocks: partials rows per iteration (size both partials arrays, and call
+ * pcs_pds_finalize_pending, with it).  pcs_pds2d_run_plan: out[6] = {paired, m, tasks of T, tasks of B,
+ * rows lo, hi of the first launch of iteration i}; nothing is launched. */
+int64_t pcs_pds2d_run_nblocks(const pcs_pds2d_args* a, int mode);
+int pcs_pds2d_run_plan(const pcs_pds2d_args* a, int mode, int64_t i, int64_t* out);
 
 /* One fused PrimalDualSplitting.update_iterand + update_diagnostics (pycsou/opt/proxalgs.py:343-394)
  * for a 2-D image with a general finite-difference K (single GPU, whole image):

@@ -151,6 +151,8 @@ _SIGS = {
     'pcs_pds2d_supported': (_c_int, [ctypes.POINTER(PdsArgs)]),
     'pcs_pds2d_path': (_c_int, [ctypes.POINTER(PdsArgs)]),
     'pcs_pds2d_run': (_c_int, [ctypes.POINTER(PdsArgs), _c_i64, _vp]),
+    'pcs_pds2d_run_nblocks': (_c_i64, [ctypes.POINTER(PdsArgs), _c_int]),
+    'pcs_pds2d_run_plan': (_c_int, [ctypes.POINTER(PdsArgs), _c_int, _c_i64, ctypes.POINTER(_c_i64)]),
     'pcs_pds2d_stencil_nblocks': (_c_i64, [ctypes.POINTER(StencilArgs)]),
     'pcs_pds2d_stencil_ws_bytes': (_c_i64, [ctypes.POINTER(StencilArgs)]),
     'pcs_pds2d_stencil_step': (_c_int, [ctypes.POINTER(StencilArgs), _vp]),

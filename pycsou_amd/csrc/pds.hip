@@ -8,6 +8,8 @@
 // with F = 1/2 ||Conv x - y||^2 (Conv separable, centred taps), 1/2 ||x - y||^2, 0, or a
 // precomputed gradient buffer; K = Gradient(kind='forward'); H = lam*L1 / lam*L21 (pixel
 // groups); G = Null / NonNegativeOrthant / Segment.  The tile kernel is in pds_tile.hpp.
+#include <cstring>
+
 #include "pds_host.hpp"
 #include "pds_pt.hpp"
 
@@ -177,9 +179,9 @@ static int launch_pt(const pcs_pds2d_args* a, RowBands rb, hipStream_t st) {
   const Slab32 s{(int)s64.n0, (int)s64.n1, (int)s64.row0, (int)s64.rows, s64.hx, s64.hy, s64.hz, s64.vec};
   const Params<float> P = make_params<float>(a);
   const float* g = FK == PCS_F_DENOISE ? (const float*)a->y : FK == PCS_F_GRADBUF ? (const float*)a->gbuf : nullptr;
-  k_pds2d_pt<FK, HK><<<(unsigned)p.ntasks + fin_extra(a), 256, 0, st>>>((const float*)a->x, (float*)a->xn, (const float*)a->z,
+  k_pds2d_pt<FK, HK><<<(unsigned)p.ntasks + fin_extra(a, p.fin_n), 256, 0, st>>>((const float*)a->x, (float*)a->xn, (const float*)a->z,
                                                          (float*)a->zn, g, s, P, a->gkind, a->partials,
-                                                         (Ctrl*)a->ctrl, a->hist, a->ws, red_out(a), p.tiles_x, p.bd,
+                                                         (Ctrl*)a->ctrl, a->hist, a->ws, red_out(a, p.fin_n), p.tiles_x, p.bd,
                                                          p.ntasks);
   return launch_status();
 }
@@ -404,12 +406,88 @@ int pcs_pds2d_step(const pcs_pds2d_args* a, hipStream_t st) {
   return PCS_EINVAL;
 }
 
+// ---- the band-paired schedule of pcs_pds2d_run.  An iteration whose arrays exceed the Infinity Cache
+// (the C3 step streams seven: x, Conv^T y, z0, z1 in, x', z0', z1' out) rereads nothing of the previous
+// iteration on-die when every launch sweeps the whole image.  Split into two row-band launches T = [0, m)
+// and B = [m, rows) whose order alternates with the iterate parity (T B | B T | T B ...), every second band
+// launch follows the previous iteration's launch on the same band with only that band's half-arrays
+// touched in between, and reads them from the cache.  tools/ic_pair_probe.hip (memory only, the step's
+// strip pattern, 4096 columns of fp32; profiles/ic_pair_probe.txt) measured the paired order against one
+// launch per iteration: 4096 rows (448 MiB in all) 79.5 against 87.9 us, 3584 rows 69.8 against 76.6, 3072
+// rows (336 MiB) 55.4 against 63.9; 2560 rows (280 MiB) 47.6 against 44.0 and 2048 rows (224 MiB, resident
+// as a whole) 31.9 against 30.2 -- so the rule pairs from 336 MiB up, and up to the largest half-set the
+// probe showed resident, 224 MiB.
+// The step kernel itself did not follow the probe: on C3 the paired loop ran 0.1129 against 0.1092 ms per
+// iteration (profiles/run_bands_ab.json), and in a kernel trace the band launch that follows its own band
+// took as long as the one that does not (67.7 and 68.0 us, profiles/run_bands_prof.json).  The schedule is
+// therefore off unless PCS_RUN_BANDS asks for it.
+constexpr int64_t kPairSetMin = 336LL << 20;   // bytes of the seven arrays, profiles/ic_pair_probe.txt
+constexpr int64_t kPairHalfMax = 224LL << 20;  // bytes of the larger band's seven half-arrays, same file
+
+struct RunPlan {
+  bool paired;
+  int64_t m, nT, nB;  // split row (on the 16-row step grid), tasks (= partials) of T and of B
+};
+
+// mode 0: one launch per iteration; 1: paired whenever the problem can run as two bands; 2: paired where the
+// size rule above says so; < 0: what PCS_RUN_BANDS says (0, 1 or auto = 2; read per call: the tests and the A/B
+// switch it), unset = 0 -- see the measurement above
+static RunPlan run_plan(const pcs_pds2d_args* a, int mode) {
+  RunPlan r{false, 0, 0, 0};
+  if (mode < 0) {
+    const char* e = getenv("PCS_RUN_BANDS");
+    mode = e == nullptr || *e == '\0' ? 0 : strcmp(e, "auto") == 0 ? 2 : atoi(e);
+  }
+  if (mode <= 0 || mode > 2 || check_args(a) != PCS_OK) return r;
+  // single images without a masked block; CONV2D's correlation passes and the stencil march's N x pass run
+  // once per iteration on the whole image
+  if (a->rows != a->n0 || a->mkind != PCS_M_NONE || a->fkind == PCS_F_CONV2D) return r;
+  if (use_smarch(a) && a->fkind == PCS_F_SEPCONV) return r;
+  if (!(use_nm64(a) || use_smarch(a) || use_march(a) || (a->kkind == PCS_K_GRAD_FORWARD && use_pt(a)))) return r;
+  const int64_t m = (a->rows / 2 + 8) / 16 * 16;
+  if (m <= 0 || m >= a->rows) return r;
+  if (mode != 1) {
+    const int64_t row = 7 * a->n1 * (a->dtype == PCS_F64 ? 8 : 4), big = m > a->rows - m ? m : a->rows - m;
+    if (a->rows * row < kPairSetMin || big * row > kPairHalfMax) return r;
+  }
+  const int64_t nT = bands_nblocks(a, RowBands{0, m, m, m}), nB = bands_nblocks(a, RowBands{m, a->rows, a->rows, a->rows});
+  if (nT < 1 || nB < 1) return r;
+  return RunPlan{true, m, nT, nB};
+}
+
+// partials per iteration of pcs_pds2d_run in `mode` (run_plan): the combined count of the two band
+// launches when paired, else pcs_pds2d_nblocks
+int64_t pcs_pds2d_run_nblocks(const pcs_pds2d_args* a, int mode) {
+  if (!a) return -1;
+  const RunPlan r = run_plan(a, mode);
+  return r.paired ? r.nT + r.nB : pcs_pds2d_nblocks(a);
+}
+
+// planning query (nothing is launched): out = {paired, m, tasks of T, tasks of B, first launch's rows lo, hi}
+// of iteration i of a run in `mode`; returns PCS_OK
+int pcs_pds2d_run_plan(const pcs_pds2d_args* a, int mode, int64_t i, int64_t* out) {
+  if (!a || !out || i < 0) return PCS_EINVAL;
+  const RunPlan r = run_plan(a, mode);
+  const bool top_first = i % 2 == 0;
+  out[0] = r.paired, out[1] = r.m, out[2] = r.nT, out[3] = r.nB;
+  out[4] = r.paired && !top_first ? r.m : 0;
+  out[5] = r.paired && top_first ? r.m : a->rows;
+  return PCS_OK;
+}
+
 // n consecutive iterations launched back to back from the host (no graph): iteration i reads
 // (x, z) when i is even and (xn, zn) when odd and writes the other pair, so after an even n the
 // iterate is back in (x, z).  Needs the in-kernel loop control (hist): after the stopping rule
 // fires the remaining launches return at once, exactly as in a captured graph.
+// Paired (run_plan, deferred finalization only): iteration i is two band launches, T then B when i is even
+// and B then T when odd.  Both write their partials into the iteration's parity array, T's tasks first
+// then B's whichever ran first; the first band launch of iteration i + 1 carries the finalizer slots and
+// reduces all nT + nB of them in that fixed order, the second carries none and, running after the first
+// has finished, sees the stop flag it may have set.  pcs_pds_finalize_pending takes the combined count
+// (pcs_pds2d_run_nblocks).
 int pcs_pds2d_run(const pcs_pds2d_args* a, int64_t n, hipStream_t st) {
   if (!a || n < 0 || !a->hist) return PCS_EINVAL;
+  const RunPlan rp = a->fin_partials ? run_plan(a, -1) : RunPlan{false, 0, 0, 0};
   pcs_pds2d_args b = *a;
   for (int64_t i = 0; i < n; ++i) {
     if (i % 2) {
@@ -421,8 +499,19 @@ int pcs_pds2d_run(const pcs_pds2d_args* a, int64_t n, hipStream_t st) {
       b.zm = a->zm, b.zmn = a->zmn;
       b.partials = a->partials, b.fin_partials = a->fin_partials;
     }
-    const int rc = pcs_pds2d_step(&b, st);
-    if (rc != PCS_OK) return rc;
+    if (!rp.paired) {
+      const int rc = pcs_pds2d_step(&b, st);
+      if (rc != PCS_OK) return rc;
+      continue;
+    }
+    double* const part = b.partials;
+    for (int k = 0; k < 2; ++k) {
+      const bool top = (k == 0) == (i % 2 == 0);
+      const int64_t lo = top ? 0 : rp.m, hi = top ? rp.m : a->rows;
+      b.partials = part + (top ? 0 : rp.nT * 4);
+      const int rc = pds2d_bands(&b, RowBands{lo, hi, hi, hi, k == 0 ? rp.nT + rp.nB : -1}, st);
+      if (rc != PCS_OK) return rc;
+    }
   }
   return PCS_OK;
 }

@@ -80,6 +80,10 @@ struct RedOut {
   const double* pre;
   int npre;
   const double* fin;  // deferred finalization (single GPU): the previous launch's partials
+  // With `fin` (a reduce-only launch never defers, so npre is free) npre tells the band launches of a
+  // paired run (pcs_pds2d_run) apart: 0 = the finalizer slots reduce as many partials as this launch has
+  // tasks; > 0 = they reduce npre partials (both band launches of the previous iteration); < 0 = this launch
+  // has no finalizer slots (the second band launch of an iteration: it only stores its partials).
 };
 
 // Entry test of a step kernel against the sticky stop flag (solver.py:65-66): true = skip the
@@ -119,7 +123,8 @@ __device__ __forceinline__ bool stop_requested(const Ctrl* ctrl, const RedOut& r
 // partials l, l + 256, ... in order, then the workgroup tree -- the same in every finalizer.
 constexpr int kFinBlocks = 8;
 constexpr int kFinLanes = 256;
-__device__ __forceinline__ int fin_shift(const RedOut& ro) { return ro.fin != nullptr ? kFinBlocks : 0; }
+__device__ __forceinline__ bool fin_slots(const RedOut& ro) { return ro.fin != nullptr && ro.npre >= 0; }
+__device__ __forceinline__ int fin_shift(const RedOut& ro) { return fin_slots(ro) ? kFinBlocks : 0; }
 
 // `red`: block_sum scratch for the launching kernel's blockDim, `flag`: one int, both LDS
 __device__ __forceinline__ void finalize_pending(const double* __restrict__ prev, int64_t nb, Ctrl* c, double* hist,
@@ -145,8 +150,8 @@ __device__ __forceinline__ void finalize_pending(const double* __restrict__ prev
 // workgroup 0 finalizes the previous launch and marks this launch's partials pending.
 __device__ __forceinline__ bool fin_slot(const RedOut& ro, int64_t nblocks, Ctrl* ctrl, double* hist, double* red,
                                          int* flag) {
-  if (ro.fin == nullptr || blockIdx.x >= kFinBlocks) return false;
-  if (blockIdx.x == 0) finalize_pending(ro.fin, nblocks, ctrl, hist, true, red, flag);
+  if (!fin_slots(ro) || blockIdx.x >= kFinBlocks) return false;
+  if (blockIdx.x == 0) finalize_pending(ro.fin, ro.npre > 0 ? ro.npre : nblocks, ctrl, hist, true, red, flag);
   return true;
 }
 

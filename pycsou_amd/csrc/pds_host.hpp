@@ -58,13 +58,14 @@ static Params<T> make_params(const pcs_pds2d_args* a) {
   return P;
 }
 
-static RedOut red_out(const pcs_pds2d_args* a) {
-  return a->hist ? RedOut{nullptr, nullptr, 0, a->fin_partials}
+// `fin_n`: RowBands::fin_n of a band launch of the paired run loop (RedOut::npre with `fin`), else 0
+static RedOut red_out(const pcs_pds2d_args* a, int64_t fin_n = 0) {
+  return a->hist ? RedOut{nullptr, nullptr, a->fin_partials ? (int)fin_n : 0, a->fin_partials}
                  : RedOut{a->sums_out, a->pre_partials, (int)a->n_pre, nullptr};
 }
 // workgroups a step launch adds ahead of its tasks (the deferred finalizer slots, pds_ctrl.hpp)
-static unsigned fin_extra(const pcs_pds2d_args* a) {
-  return a->hist && a->fin_partials ? (unsigned)kFinBlocks : 0u;
+static unsigned fin_extra(const pcs_pds2d_args* a, int64_t fin_n = 0) {
+  return a->hist && a->fin_partials && fin_n >= 0 ? (unsigned)kFinBlocks : 0u;
 }
 
 // ---- fp32 separable conv, tiers 3 and 7: the row-marching kernel (pds_march.hpp) on every
@@ -76,18 +77,23 @@ struct MarchPlan {
   int tiles_x;  // 64-column strips
   Bands bd;     // row segments of the launch's bands
   int ntasks;   // strips x segments
+  int64_t fin_n = 0;  // RowBands::fin_n of the launch
   StripSplit sp{-1, 0, 0, 0, {0, 0, 0}, Bands{16, 0, 0, 0, 0, 0}};  // border strips on shorter segments (sm_plan)
 };
 
 // own-row bands [ra0, rb0) and [ra1, rb1) of a launch (0 <= ra0 <= rb0 <= ra1 <= rb1 <= rows)
+// fin_n: the launch's place in the paired run loop (RunPlan below; RedOut::npre of a deferring launch) --
+// 0 = an ordinary launch, > 0 = its finalizer slots reduce fin_n partials, < 0 = it has no finalizer slots
 struct RowBands {
   int64_t ra0, rb0, ra1, rb1;
+  int64_t fin_n = 0;
 };
 static RowBands full_bands(const pcs_pds2d_args* a) { return RowBands{0, a->rows, a->rows, a->rows}; }
 
 // Segments of TS-row steps over the bands: about `slots / tiles_x` segments in all (one wave of
 // resident workgroups), at least one per non-empty band, at most one per `min_steps` steps.
 static void plan_bands(RowBands rb, int TS, int tiles_x, int slots, int min_steps, MarchPlan* p) {
+  p->fin_n = rb.fin_n;
   if (rb.rb0 == rb.ra0) rb = RowBands{rb.ra1, rb.rb1, rb.rb1, rb.rb1};
   const int64_t L0 = rb.rb0 - rb.ra0, L1 = rb.rb1 - rb.ra1;
   const int64_t steps = (L0 + TS - 1) / TS + (L1 + TS - 1) / TS;

@@ -519,6 +519,7 @@ int nm64_slots() {
 bool nm64_plan(const pcs_pds2d_args* a, RowBands rb, MarchPlan* p) {
   const int tiles_x = (int)((a->n1 + 59) / 60);
   if (tiles_x < 2) return false;
+  p->fin_n = rb.fin_n;
   if (rb.rb0 == rb.ra0) rb = RowBands{rb.ra1, rb.rb1, rb.rb1, rb.rb1};
   const int64_t L0 = rb.rb0 - rb.ra0, L1 = rb.rb1 - rb.ra1;
   const int64_t steps = (L0 + 31) / 32 + (L1 + 31) / 32;
@@ -548,9 +549,9 @@ static int nm64_go(const pcs_pds2d_args* a, const MarchPlan& p, hipStream_t st) 
   const Slab32 s{(int)s64.n0, (int)s64.n1, (int)s64.row0, (int)s64.rows, s64.hx, s64.hy, s64.hz, s64.vec};
   const Params<double> P = make_params<double>(a);
   nm64_attr<H, HK, KK>();
-  k_pds2d_nmarch64<H, HK, KK><<<(unsigned)p.ntasks + fin_extra(a), 512, NM64<H>::SZ * sizeof(double), st>>>(
+  k_pds2d_nmarch64<H, HK, KK><<<(unsigned)p.ntasks + fin_extra(a, p.fin_n), 512, NM64<H>::SZ * sizeof(double), st>>>(
       (const double*)a->x, (double*)a->xn, (const double*)a->z, (double*)a->zn, (const double*)a->cty,
-      (const double*)a->ntaps, s, P, a->gkind, a->edge, a->partials, (Ctrl*)a->ctrl, a->hist, a->ws, red_out(a),
+      (const double*)a->ntaps, s, P, a->gkind, a->edge, a->partials, (Ctrl*)a->ctrl, a->hist, a->ws, red_out(a, p.fin_n),
       p.tiles_x, p.bd, p.ntasks);
   return launch_status();
 }

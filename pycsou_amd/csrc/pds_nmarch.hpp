@@ -107,6 +107,13 @@ __device__ __forceinline__ G4<float> bload4a(Rsrc r, uint32_t off) {
 #define PCS_NM_XEARLY 1
 #endif
 
+// forward kernel: the G = 0 problem (gk == PCS_G_NULL, the C3 benchmark's) runs a copy of the task compiled
+// with that constant (1), so that prox_g's scalar branches on gk -- one per element, four per thread and
+// step -- and the live gk / seg_a / seg_b leave its loop; other G keep the general copy.  0: one copy
+#ifndef PCS_NM_GKSPLIT
+#define PCS_NM_GKSPLIT 1
+#endif
+
 // forward kernel: the strip's 65th column by 16 lanes per output (1) or by the last group's 4 lanes
 // per wave in a serial 29-read branch (0)
 #ifndef PCS_NM_COOP65
@@ -1060,8 +1067,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PCS_NM_WPE))
   const int c0 = strip * M::TW;
 
   double part[4] = {0.0, 0.0, 0.0, 0.0};
-  if (!stopped)
-    nmarch_task<T, H, HK, NT, PCS_FORWARD>(x, xn, z, zn, b, tq, s, P, gk, 0, s0, s1, c0, sm, zs0, zs1, part, stop_raw);
+  if (!stopped) {
+    if (PCS_NM_GKSPLIT && gk == PCS_G_NULL)  // uniform
+      nmarch_task<T, H, HK, NT, PCS_FORWARD>(x, xn, z, zn, b, tq, s, P, PCS_G_NULL, 0, s0, s1, c0, sm, zs0, zs1, part,
+                                             stop_raw);
+    else
+      nmarch_task<T, H, HK, NT, PCS_FORWARD>(x, xn, z, zn, b, tq, s, P, gk, 0, s0, s1, c0, sm, zs0, zs1, part, stop_raw);
+  }
   if (stop_raw) return;  // the task returned before any store
   block_sum<4>(part, red);
   publish_partials(part, partials, ntasks, ws, ctrl, hist, flag, ro);

@@ -295,7 +295,17 @@ class PDS2DEngine:
         """[nblocks][4] partials; with deferred finalization two such arrays, swapped with the
         iterate parity (the launch of parity p writes array p and finalizes array 1 - p)."""
         self.defer = DEFER_FIN and isinstance(a, L.PdsArgs)
-        nb4 = self.nblocks * 4
+        # pcs_pds2d_run may run an iteration as two row-band launches (the band-paired schedule, csrc/pds.hip),
+        # which leave the partials of both: run_nblocks is the count its launches write and its flush reduces;
+        # the arrays hold the largest count any PCS_RUN_BANDS setting can ask for
+        self.run_nblocks = cap = self.nblocks
+        if self.defer:
+            a.x, a.xn = self.X[0].data_ptr(), self.X[1].data_ptr()
+            a.z, a.zn = self.Z[0].data_ptr(), self.Z[1].data_ptr()
+            a.partials = a.x  # placeholder for the planning query (never written)
+            self.run_nblocks = int(self.lib.pcs_pds2d_run_nblocks(ctypes.byref(a), -1))
+            cap = max(cap, self.run_nblocks, int(self.lib.pcs_pds2d_run_nblocks(ctypes.byref(a), 1)))
+        nb4 = cap * 4
         self.partials = torch.empty((2 if self.defer else 1) * nb4, dtype=torch.float64, device=dev)
         self.part_halves = [self.partials[:nb4], self.partials[nb4:]] if self.defer else [self.partials]
         a.partials = self.partials.data_ptr()
@@ -309,11 +319,13 @@ class PDS2DEngine:
         if getattr(self, 'defer', False):
             a.partials, a.fin_partials = self.part_halves[p].data_ptr(), self.part_halves[1 - p].data_ptr()
 
-    def _flush(self, next_p, hist):
+    def _flush(self, next_p, hist, run=False):
         """Deferred finalization: finalize the last launch's partials (parity 1 - next_p) if they
-        are pending (pcs_pds_finalize_pending; a no-op when the loop has stopped)."""
+        are pending (pcs_pds_finalize_pending; a no-op when the loop has stopped).  `run`: the last
+        iteration came from pcs_pds2d_run (its partials count), not from a single step."""
         if getattr(self, 'defer', False):
-            L.check(self.lib.pcs_pds_finalize_pending(L.ptr(self.part_halves[1 - next_p]), self.nblocks,
+            L.check(self.lib.pcs_pds_finalize_pending(L.ptr(self.part_halves[1 - next_p]),
+                                                      self.run_nblocks if run else self.nblocks,
                                                       L.ptr(self.ctrl), L.ptr(hist), L.stream()),
                     'pcs_pds_finalize_pending')
 
@@ -398,7 +410,7 @@ class PDS2DEngine:
             a.hist = self.hist.data_ptr()
             self._run_call(int(n))
             self._fixed_p = p ^ (int(n) & 1)
-            self._flush(self._fixed_p, self.hist)
+            self._flush(self._fixed_p, self.hist, run=True)
             return
         while n >= self.chunk and p == 0:
             self.graph.replay()
@@ -520,7 +532,7 @@ class PDS2DEngine:
                 if int(self.ctrl.view(torch.int32)[1].item()) != 0:
                     break
         hist = self.hist
-        self._flush(0, hist)  # every chunk is an even number of launches
+        self._flush(0, hist, run=self.native)  # every chunk is an even number of launches
         torch.cuda.synchronize()
         c = self.ctrl.view(torch.int32)[:2].cpu().numpy()
         n = int(c[0])
