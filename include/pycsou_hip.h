@@ -377,6 +377,49 @@ int pcs_pds2d_run(const pcs_pds2d_args* a, int64_t n, hipStream_t stream);
 int64_t pcs_pds2d_run_nblocks(const pcs_pds2d_args* a, int mode);
 int pcs_pds2d_run_plan(const pcs_pds2d_args* a, int mode, int64_t i, int64_t* out);
 
+/* ---------------------------------------------------------------- fused APGD iteration */
+
+/* One fused AcceleratedProximalGradientDescent.update_iterand + update_diagnostics + loop test
+ * (pycsou/opt/proxalgs.py:586-622, pycsou/core/solver.py:65-66) in ONE launch, for a whole 2-D image and
+ * F = (1/2) ||Conv x - y||^2 with a separable Conv of half width <= 7:
+ *   g    = N x - cty              N = Conv^T Conv as two 29-tap passes (exact zero-boundary edge rows)
+ *   x_t  = G.prox(x - tau g, tau) gkind PCS_G_NULL / PCS_G_NONNEG / PCS_G_SEGMENT [seg_a, seg_b] /
+ *                                 PCS_APGD_G_L1 (lam * L1Norm: soft threshold tau*lam)
+ *   x'   = x_t + a (x_t - aux)    aux = the previous x_t ('past_aux'), a = (t_old - 1) / t
+ * writes x' -> xn, x_t -> aux_n, reduces ||x - x'||^2 and ||x||^2 inside the launch and runs the loop
+ * control of pcs_pds_finalize on them (the dual pair of `hist` reads inf; init the control block with
+ * has_dual = 0).  A launch that finds the stop flag set stores nothing.  Per element the arithmetic is
+ * pcs_apgd_step's; only grad F is formed differently (N x - Conv^T y instead of Conv^T (Conv x - y)).
+ * Takes n0, n1 >= 16, n1 % 4 == 0, half <= 7, n0 * n1 * sizeof(T) < 2^30, every array n0 * n1 elements
+ * and 16-B aligned, x / aux / cty distinct from xn / aux_n (a workgroup reads rows of x that its
+ * neighbours write in xn): pcs_apgd2d_supported is 0 and the calls return PCS_EUNSUPPORTED otherwise. */
+typedef struct {
+  int dtype;          /* PCS_F32 / PCS_F64 */
+  int gkind;          /* PCS_G_* / PCS_APGD_G_L1 */
+  int64_t n0, n1;     /* image */
+  int half;           /* separable conv half width H (taps 2H+1, centred) */
+  int pad;
+  const void* taps0;  /* 2H+1 taps along axis 0 (rows), device */
+  const void* taps1;  /* 2H+1 taps along axis 1 (cols), device */
+  double tau, lam, seg_a, seg_b;
+  const void* x; void* xn; const void* aux; void* aux_n;
+  const void* cty;    /* Conv^T y, formed once by the caller */
+  double* partials;   /* [pcs_apgd2d_nblocks()][4] */
+  void* ctrl;         /* device control block (pcs_ctrl_init2, has_dual 0) */
+  double* hist;       /* 2 doubles per iteration: the relative improvement, inf */
+  void* ws;           /* pcs_apgd2d_ws_bytes() bytes, zeroed once before first use */
+} pcs_apgd2d_args;
+int pcs_apgd2d_supported(const pcs_apgd2d_args* a);
+int64_t pcs_apgd2d_nblocks(const pcs_apgd2d_args* a);
+int64_t pcs_apgd2d_ws_bytes(const pcs_apgd2d_args* a);
+/* One iteration (x, aux -> xn, aux_n) with momentum coefficient a. */
+int pcs_apgd2d_step(const pcs_apgd2d_args* a, double a_coef, hipStream_t stream);
+/* n iterations launched back to back, ping-ponging (x, aux) <-> (xn, aux_n); launch i uses a_host[i]
+ * (host memory, read before the call returns).  The coefficients depend on the iteration index alone, so
+ * the host always knows them, and once the loop has stopped every later launch is a no-op: the iterate
+ * after Ctrl.it iterations is in (x, aux) when Ctrl.it - (Ctrl.it at the call) is even, else in (xn, aux_n). */
+int pcs_apgd2d_run(const pcs_apgd2d_args* a, const double* a_host, int64_t n, hipStream_t stream);
+
 /* One fused PrimalDualSplitting.update_iterand + update_diagnostics (pycsou/opt/proxalgs.py:343-394)
  * for a 2-D image with a general finite-difference K (single GPU, whole image):
  *   kkind PCS_K_GRAD_{FORWARD,BACKWARD,CENTERED}: K = Gradient(kind, edge, step)  (diff.py:777-882),

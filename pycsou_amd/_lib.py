@@ -73,6 +73,15 @@ class Pds3Args(ctypes.Structure):
                 ('conv0_w', _vp), ('conv0_taps', _vp), ('conv0_k', _c_int), ('conv0_off', _c_int)]
 
 
+class Apgd2dArgs(ctypes.Structure):
+    """Mirror of pcs_apgd2d_args."""
+    _fields_ = [('dtype', _c_int), ('gkind', _c_int), ('n0', _c_i64), ('n1', _c_i64),
+                ('half', _c_int), ('pad', _c_int), ('taps0', _vp), ('taps1', _vp),
+                ('tau', _c_dbl), ('lam', _c_dbl), ('seg_a', _c_dbl), ('seg_b', _c_dbl),
+                ('x', _vp), ('xn', _vp), ('aux', _vp), ('aux_n', _vp), ('cty', _vp),
+                ('partials', _vp), ('ctrl', _vp), ('hist', _vp), ('ws', _vp)]
+
+
 class HaloSet(ctypes.Structure):
     """Mirror of pcs_halo_set."""
     _fields_ = [('nbuf', _c_int), ('pad', _c_int), ('send_lo', _vp * 4), ('recv_lo', _vp * 4),
@@ -143,6 +152,11 @@ _SIGS = {
     'pcs_pds2d_nblocks': (_c_i64, [ctypes.POINTER(PdsArgs)]),
     'pcs_pds2d_ws_bytes': (_c_i64, [ctypes.POINTER(PdsArgs)]),
     'pcs_pds2d_step': (_c_int, [ctypes.POINTER(PdsArgs), _vp]),
+    'pcs_apgd2d_supported': (_c_int, [ctypes.POINTER(Apgd2dArgs)]),
+    'pcs_apgd2d_nblocks': (_c_i64, [ctypes.POINTER(Apgd2dArgs)]),
+    'pcs_apgd2d_ws_bytes': (_c_i64, [ctypes.POINTER(Apgd2dArgs)]),
+    'pcs_apgd2d_step': (_c_int, [ctypes.POINTER(Apgd2dArgs), _c_dbl, _vp]),
+    'pcs_apgd2d_run': (_c_int, [ctypes.POINTER(Apgd2dArgs), _pdbl, _c_i64, _vp]),
     'pcs_fftconv2d_grid': (_c_i64, [_c_i64, _c_int]),
     'pcs_fftconv2d_create': (_c_int, [_c_int, _c_i64, _c_i64, _pdbl, _c_int, _c_int, _c_int, _c_int,
                                       ctypes.POINTER(_vp)]),

@@ -215,6 +215,159 @@ def match_pds2d(F, G, H, K, has_H):
     return None
 
 
+def apgd_g_kind(G):
+    """(kind, lam, seg) of an APGD G the fused steps take (pcs_apgd_step, pcs_apgd2d_step): null,
+    lam * L1Norm, NonNegativeOrthant or Segment; None otherwise."""
+    lam = 1.0
+    if isinstance(G, ProxFuncPostComp) and G.shift == 0 and isinstance(G.prox_func, L1Norm):
+        G, lam = G.prox_func, float(G.scale)
+    if G is None or isinstance(G, NullProximableFunctional):
+        return L.PCS_G_NULL, 1.0, (0.0, 1.0)
+    if isinstance(G, L1Norm):
+        return L.PCS_APGD_G_L1, lam, (0.0, 1.0)
+    if isinstance(G, IndicatorFunctional) and G.kind == 'nonneg':
+        return L.PCS_G_NONNEG, 1.0, (0.0, 1.0)
+    if isinstance(G, IndicatorFunctional) and G.kind == 'segment':
+        return L.PCS_G_SEGMENT, 1.0, tuple(G.params)
+    return None
+
+
+def sep_rtol(dtype):
+    """How close to rank one a PSF must be to run as two 1-D passes in `dtype`."""
+    return 2e-7 if dtype == torch.float32 else 1e-13
+
+
+def match_apgd2d(F, G, dtype=torch.float64):
+    """Engine spec if (F, G) is a fused-APGD problem: F = (1/2) * SquaredL2Loss(y) * Convolve2D with a
+    PSF that is separable to the tolerance of `dtype` and reaches <= 7 samples either side, G null /
+    lam * L1Norm / NonNegativeOrthant / Segment; None otherwise."""
+    if not (isinstance(F, DiffMapComp) and isinstance(F.map2, Convolve2DOp)):
+        return None
+    conv = F.map2
+    shape = tuple(conv.dims)
+    s = _half_loss_data(F.map1)
+    if len(shape) != 2 or s is None or O.numel(s) != shape[0] * shape[1]:
+        return None
+    gk = apgd_g_kind(G)
+    if gk is None:
+        return None
+    sep = conv.separable(rtol=sep_rtol(dtype))
+    if sep is None or sep[2] > 7:
+        return None
+    return {'apgd': True, 'shape': shape, 'shift': s, 'conv': conv, 'sep': sep, 'gkind': gk[0], 'lam': gk[1],
+            'seg': gk[2]}
+
+
+def apgd_momentum(acceleration, d, k, t_old):
+    """(t, a) of APGD iteration k (pycsou/opt/proxalgs.py:592-598): a = (t_old - 1) / t multiplies
+    (x_t - past_aux).  'CD' reads the iteration index, 'BT' the previous t, anything else has no momentum."""
+    if acceleration == 'BT':
+        t = (1 + np.sqrt(1 + 4 * t_old ** 2)) / 2
+    elif acceleration == 'CD':
+        t = (k + d) / d
+    else:
+        t = t_old = 1
+    return t, (t_old - 1) / t
+
+
+def apgd_coeffs(acceleration, d, k0, n, t_old):
+    """The coefficients a of iterations k0 .. k0 + n - 1 continuing from t_old, and the last t."""
+    out = []
+    for k in range(k0, k0 + n):
+        t_old, a = apgd_momentum(acceleration, d, k, t_old)
+        out.append(a)
+    return out, t_old
+
+
+class APGD2DEngine:
+    """Device state + loop of one fused 2-D APGD problem (match_apgd2d): every iteration is ONE launch
+    (pcs_apgd2d_step: grad F by the two-pass normal-operator march, G.prox, the momentum step, the
+    diagnostics' norms and the loop test), launched from C in chunks (pcs_apgd2d_run) with the chunk's
+    momentum coefficients from the host; the control block is read once per chunk."""
+
+    def __init__(self, spec, dtype, tau, x0, acceleration='CD', d=75., chunk=32):
+        self.lib = L.gpu()
+        self.spec, self.dtype = spec, dtype
+        self.acceleration, self.d = acceleration, d
+        n0, n1 = spec['shape']
+        self.N = n0 * n1
+        self.x0 = x0.to(dtype)
+        dev = self.x0.device
+        self.X = [torch.empty(self.N, dtype=dtype, device=dev) for _ in range(2)]
+        self.AUX = [torch.empty(self.N, dtype=dtype, device=dev) for _ in range(2)]
+        self.chunk = max(2, chunk + (chunk % 2))
+        t0, t1, half = spec['sep']
+        self.taps = [torch.as_tensor(t).to(device=dev, dtype=dtype) for t in (t0, t1)]
+        # Conv^T y formed once in fp64 (y = -shift exactly)
+        self.cty = spec['conv']._adj(-O.to_dev(spec['shift'], torch.float64)).to(dtype).contiguous()
+        a = L.Apgd2dArgs()
+        a.dtype = L.PCS_F32 if dtype == torch.float32 else L.PCS_F64
+        a.gkind, a.n0, a.n1, a.half = spec['gkind'], n0, n1, half
+        a.taps0, a.taps1 = self.taps[0].data_ptr(), self.taps[1].data_ptr()
+        a.tau, a.lam = float(tau), float(spec['lam'])
+        a.seg_a, a.seg_b = spec['seg']
+        a.x, a.xn = self.X[0].data_ptr(), self.X[1].data_ptr()
+        a.aux, a.aux_n = self.AUX[0].data_ptr(), self.AUX[1].data_ptr()
+        a.cty = self.cty.data_ptr()
+        self.args = a
+        if self.lib.pcs_apgd2d_supported(ctypes.byref(a)) != 1:
+            raise ValueError('problem not supported by the fused APGD step')
+        self.nblocks = int(self.lib.pcs_apgd2d_nblocks(ctypes.byref(a)))
+        self.partials = torch.empty(4 * self.nblocks, dtype=torch.float64, device=dev)
+        self.ctrl = torch.zeros(int(self.lib.pcs_ctrl_bytes()) // 8, dtype=torch.float64, device=dev)
+        # the reduction counters start at 0 and every launch leaves them at 0
+        self.ws = torch.zeros(int(self.lib.pcs_apgd2d_ws_bytes(ctypes.byref(a))) // 8 + 2, dtype=torch.float64,
+                              device=dev)
+        a.partials, a.ctrl, a.ws = self.partials.data_ptr(), self.ctrl.data_ptr(), self.ws.data_ptr()
+        self.hist = None
+        self.ctrl_host = torch.zeros(2, dtype=torch.int32).pin_memory()
+
+    def coeffs(self, k0, n, t_old):
+        return apgd_coeffs(self.acceleration, self.d, k0, n, t_old)
+
+    def start(self, max_iter, min_iter, thr, total=None):
+        """Iterate x0, past_aux 0, a fresh loop control and a history with room for the first chunks."""
+        total = max(int(min_iter), int(max_iter)) + 1 if total is None else total
+        hist_len = 2 * min(total, max(HIST_CHUNK, 2 * self.chunk)) + 2
+        if self.hist is None or self.hist.numel() < hist_len:
+            self.hist = torch.empty(hist_len, dtype=torch.float64, device=self.x0.device)
+        self.hist.fill_(float('nan'))
+        self.X[0].copy_(self.x0)
+        self.AUX[0].zero_()
+        L.check(self.lib.pcs_ctrl_init2(L.ptr(self.ctrl), int(min_iter), int(max_iter), float(thr), 0,
+                                        int(self.hist.numel()), L.stream()), 'pcs_ctrl_init2')
+        return total
+
+    def launch(self, coeffs):
+        """len(coeffs) (even) iterations from buffer parity 0, launched back to back."""
+        self.args.hist = self.hist.data_ptr()
+        L.check(self.lib.pcs_apgd2d_run(ctypes.byref(self.args), L.dbls(coeffs), len(coeffs), L.stream()),
+                'pcs_apgd2d_run')
+
+    def run(self, max_iter, min_iter, accuracy_threshold):
+        """The reference loop from x0 (solver.py:55-76): (n, x, past_aux, past_t, hist[n])."""
+        total = self.start(max_iter, min_iter, accuracy_threshold)
+        n_chunks = -(-total // self.chunk)
+        t_old, pending = 1, []
+        for k in range(n_chunks):
+            self.hist = grow_hist(self.hist, self.ctrl, (k + 1) * self.chunk + 1, total)
+            coeffs, t_old = self.coeffs(k * self.chunk, self.chunk, t_old)
+            self.launch(coeffs)
+            ev = torch.cuda.Event()
+            self.ctrl_host.copy_(self.ctrl.view(torch.int32)[:2], non_blocking=True)
+            ev.record()
+            pending.append(ev)
+            if len(pending) >= 2:  # one chunk in flight behind the one whose control is read
+                pending.pop(0).synchronize()
+                if int(self.ctrl_host[1]) != 0:
+                    break
+        torch.cuda.synchronize()
+        n = int(self.ctrl.view(torch.int32)[:1].cpu()[0])
+        h = self.hist[:2 * n].cpu().numpy().reshape(n, 2)[:, 0].copy() if n > 0 else np.zeros((0,))
+        past_t = self.coeffs(0, n, 1)[1]
+        return n, self.X[n % 2], self.AUX[n % 2], past_t, h
+
+
 class PDS2DEngine:
     """Device state + captured loop for one fused 2-D PDS problem."""
 

@@ -542,8 +542,10 @@ class AcceleratedProximalGradientDescent(GenericIterativeAlgorithm):
     """Accelerated proximal gradient descent (``pycsou/opt/proxalgs.py:400-622``)."""
 
     def __init__(self, dim, F=None, G=None, tau=None, acceleration='CD', beta=None, x0=None, max_iter=500,
-                 min_iter=10, accuracy_threshold=1e-3, verbose=1, d=75.):
+                 min_iter=10, accuracy_threshold=1e-3, verbose=1, d=75., engine=None):
         self.dim = dim
+        self.engine_mode = engine
+        self._engine = None
         self.acceleration = acceleration
         self.d = d
         if isinstance(F, DifferentiableMap):
@@ -594,10 +596,67 @@ class AcceleratedProximalGradientDescent(GenericIterativeAlgorithm):
     def _out(self, t):
         return t if self._torch_out else t.detach().cpu().numpy()
 
+    # fused engine: iterations per chunk launched from C (tests set it)
+    ENGINE_CHUNK = 32
+
+    def _fused_spec(self, dtype):
+        """The fused-engine spec of this problem (``engine.match_apgd2d``) under ``engine_mode``: False =
+        never, 'fused' = required (ValueError otherwise), None = when the problem matches, a GPU is
+        visible and the library takes the image."""
+        if self.engine_mode is False:
+            return None
+        from .engine import match_apgd2d
+        F = None if isinstance(self.F, NullDifferentiableFunctional) else self.F
+        spec = match_apgd2d(F, self.G, dtype)
+        if spec is not None and (not torch.cuda.is_available() or not self._engine_takes(spec, dtype)):
+            spec = None
+        if spec is None and self.engine_mode == 'fused':
+            raise ValueError('problem does not match the fused APGD engine')
+        return spec
+
+    @staticmethod
+    def _engine_takes(spec, dtype):
+        """pcs_apgd2d_supported on the problem's geometry (the buffers themselves are allocated aligned)."""
+        import ctypes
+        from .. import _lib as L
+        a = L.Apgd2dArgs()
+        a.dtype = L.PCS_F32 if dtype == torch.float32 else L.PCS_F64
+        a.gkind, (a.n0, a.n1), a.half = spec['gkind'], spec['shape'], spec['sep'][2]
+        a.tau, a.lam = 1.0, 1.0
+        for i, f in enumerate(('taps0', 'taps1', 'x', 'xn', 'aux', 'aux_n', 'cty')):
+            setattr(a, f, 4096 * (i + 1))  # distinct aligned stand-ins: nothing is dereferenced
+        return L.load().pcs_apgd2d_supported(ctypes.byref(a)) == 1
+
+    def _iterate_fused(self, spec, dtype):
+        from .engine import APGD2DEngine
+        x0 = O.to_dev(self.x0, dtype)
+        self._engine = APGD2DEngine(spec, dtype, self.tau, x0, acceleration=self.acceleration, d=self.d,
+                                    chunk=self.ENGINE_CHUNK)
+        n, x, aux, t, hist = self._engine.run(self.max_iter, self.min_iter, self.accuracy_threshold)
+        self.iter = n
+        rows = [[i, hist[i]] for i in range(n)]
+        self.diagnostics = _frame(['Iter', 'Relative Improvement'], rows)
+        if self.verbose is not None:
+            # the fused loop never stops for the host: the reference's lines (solver.py:69-71) are printed
+            # from the device history once the run ends, as the fused PDS path does
+            for row in rows[::self.verbose]:
+                self._rows = [row]
+                self.print_diagnostics()
+        self._rows = rows
+        self._state = (x, aux, t)
+        self.converged = True
+        self.iterand = {'iterand': self._out(x), 'past_aux': self._out(aux), 'past_t': t}
+        return self.iterand, self.converged, self.diagnostics
+
     def iterate(self):
-        """The reference loop (solver.py:55-76) with the stopping rule evaluated on the device
-        (``_DeviceLoop``; the fused step writes its two norms straight into the loop's sums)."""
+        """The reference loop (solver.py:55-76).  A separable-blur image problem runs on the fused engine
+        (one launch per iteration, ``engine.APGD2DEngine``); every other problem, and ``engine=False``,
+        operator by operator with the stopping rule evaluated on the device (``_DeviceLoop``; the fused
+        pointwise step writes its two norms straight into the loop's sums)."""
         dtype = self._compute_dtype()
+        spec = self._fused_spec(dtype)
+        if spec is not None:
+            return self._iterate_fused(spec, dtype)
         x0 = O.to_dev(self.x0, dtype)
         loop = _DeviceLoop(self.max_iter, self.min_iter, self.accuracy_threshold, False, x0.device)
         if self.verbose is not None:
@@ -632,31 +691,12 @@ class AcceleratedProximalGradientDescent(GenericIterativeAlgorithm):
 
     def _g_kind(self):
         """(kind, lam, seg) of G for the fused step (pcs_apgd_step), or None."""
-        from .. import _lib as L
-        from ..core.functional import ProxFuncPostComp
-        from ..func.base import IndicatorFunctional
-        from ..func.penalty import L1Norm
-        G, lam = self.G, 1.0
-        if isinstance(G, ProxFuncPostComp) and G.shift == 0 and isinstance(G.prox_func, L1Norm):
-            G, lam = G.prox_func, float(G.scale)
-        if isinstance(G, NullProximableFunctional):
-            return L.PCS_G_NULL, 1.0, (0.0, 1.0)
-        if isinstance(G, L1Norm):
-            return L.PCS_APGD_G_L1, lam, (0.0, 1.0)
-        if isinstance(G, IndicatorFunctional) and G.kind == 'nonneg':
-            return L.PCS_G_NONNEG, 1.0, (0.0, 1.0)
-        if isinstance(G, IndicatorFunctional) and G.kind == 'segment':
-            return L.PCS_G_SEGMENT, 1.0, tuple(G.params)
-        return None
+        from .engine import apgd_g_kind
+        return apgd_g_kind(self.G)
 
     def _momentum(self, t_old):
-        if self.acceleration == 'BT':
-            t = (1 + np.sqrt(1 + 4 * t_old ** 2)) / 2
-        elif self.acceleration == 'CD':
-            t = (self.iter + self.d) / self.d
-        else:
-            t = t_old = 1
-        return t, (t_old - 1) / t
+        from .engine import apgd_momentum
+        return apgd_momentum(self.acceleration, self.d, self.iter, t_old)
 
     def _update_dev(self, st, sums_out=None):
         """``proxalgs.py:586-601``: G.prox, the momentum step and the diagnostics' two norms in
