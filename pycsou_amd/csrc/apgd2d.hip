@@ -31,18 +31,11 @@ static void apgd_attr() {
 // resident workgroups of the APGD march on the device (queried once per type)
 template <typename T>
 static int apgd_slots() {
-  static int slots = 0;
-  if (slots == 0) {
-    int dev = 0, cus = 0, nb = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                hipSuccess || cus < 1)
-      cus = 256;
+  static const int slots = [] {
     apgd_attr<T>();
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, apgd_fn<T>(), 256, nrm_lds<T>()) != hipSuccess || nb < 1)
-      nb = 1;
-    (void)hipGetLastError();
-    slots = cus * nb;
-  }
+    const Occupancy o = occupancy(apgd_fn<T>(), 256, nrm_lds<T>(), 1);
+    return o.cus * o.per_cu;
+  }();
   return slots;
 }
 

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/pycsou_hip.h"
 
@@ -14,6 +15,28 @@ constexpr int kWave = 64;
 inline int launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? PCS_OK : PCS_ELAUNCH;
+}
+
+// Resident workgroups of a kernel: the current device's CU count (256 if there is none) and the blocks per CU
+// at `threads` threads and `lds` bytes of dynamic LDS (`fallback` if the query fails or gives < 1).  Leaves no
+// sticky error behind.  Callers cache the result and apply their own clamp, rounds and override.
+struct Occupancy {
+  int cus, per_cu;
+};
+template <typename K>
+inline Occupancy occupancy(K kernel, int threads, size_t lds, int fallback) {
+  int dev = 0, cus = 0, nb = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+    cus = 256;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, threads, lds) != hipSuccess || nb < 1) nb = fallback;
+  (void)hipGetLastError();
+  return Occupancy{cus, nb};
+}
+// diagnostics (grid-size sweeps): a positive integer in the environment variable `name` replaces `v`
+inline int env_override(const char* name, int v) {
+  const char* e = getenv(name);
+  return e && atoi(e) > 0 ? atoi(e) : v;
 }
 
 inline unsigned grid_for(int64_t n, int block, unsigned cap = 8192) {

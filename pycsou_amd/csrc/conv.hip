@@ -757,19 +757,10 @@ __global__ __launch_bounds__(256) void k_sep2d_march(const T* __restrict__ in, T
 // resident workgroups of k_sep2d_march<T> on the device (queried once per type)
 template <typename T>
 static int sep_march_slots() {
-  static int slots = 0;
-  if (slots == 0) {
-    int dev = 0, cus = 0, nb = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                hipSuccess || cus < 1)
-      cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_sep2d_march<T, 0, true>, 256, 0) != hipSuccess || nb < 1)
-      nb = 2;
-    (void)hipGetLastError();
-    slots = cus * nb;
-    const char* e = getenv("PCS_SEP2D_SLOTS");  // diagnostics: grid-size sweep
-    if (e && atoi(e) > 0) slots = atoi(e);
-  }
+  static const int slots = [] {
+    const Occupancy o = occupancy(k_sep2d_march<T, 0, true>, 256, 0, 2);
+    return env_override("PCS_SEP2D_SLOTS", o.cus * o.per_cu);
+  }();
   return slots;
 }
 

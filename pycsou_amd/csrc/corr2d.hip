@@ -377,16 +377,9 @@ static int tier(int kh, int kw, int off0, int off1) {
 template <typename T, int K, bool FLIP, bool VEC>
 static int slots_for() {
   static const int slots = [] {
-    int dev = 0, cus = 256, nb = 1;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_corr2d<T, K, FLIP, VEC>, 256,
-                                                     Cfg<T, K>::LDS_BYTES) != hipSuccess ||
-        nb < 1)
-      nb = 1;
-    const char* e = getenv("PCS_CORR_ROUNDS");  // diagnostics: rounds of the resident workgroups
-    const int rounds = e && atoi(e) > 0 ? atoi(e) : 1;
-    return cus * nb * rounds;
+    const Occupancy o = occupancy(k_corr2d<T, K, FLIP, VEC>, 256, Cfg<T, K>::LDS_BYTES, 1);
+    // PCS_CORR_ROUNDS (diagnostics): rounds of the resident workgroups
+    return o.cus * o.per_cu * env_override("PCS_CORR_ROUNDS", 1);
   }();
   return slots;
 }

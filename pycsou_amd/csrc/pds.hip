@@ -107,7 +107,7 @@ __global__ __launch_bounds__(kFinLanes) void k_finalize_pending(const double* __
   finalize_pending(part, np, c, hist, false, red, flag);
 }
 
-// ---------------------------------------------------------------- host dispatch (planning: pds_host.hpp)
+// ---------------------------------------------------------------- host dispatch (select_path: pds_host.hpp)
 template <typename T, int FK, int H>
 static int launch_pds2d(const pcs_pds2d_args* a, hipStream_t st) {
   constexpr int TH = Tile<T>::TH, NT = Tile<T>::NT;
@@ -124,91 +124,8 @@ static int launch_pds2d(const pcs_pds2d_args* a, hipStream_t st) {
   return launch_status();
 }
 
-// ---- fp32 pointwise grad F (NULL / DENOISE / GRADBUF): the row-marching kernel of pds_pt.hpp
-static int pt_slots() {
-  static int slots = 0;
-  if (slots == 0) {
-    int dev = 0, cus = 0, nb = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                hipSuccess || cus < 1)
-      cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_pds2d_pt<PCS_F_DENOISE, PCS_H_L21>, 256, 0) !=
-            hipSuccess ||
-        nb < 1)
-      nb = 4;
-    (void)hipGetLastError();
-    // 2 workgroups per CU (fewer, longer row segments) although 5 fit: C2 2048^2 with the deferred
-    // finalization 41.6-43.1 K it/s at 512 workgroups against 40.6-41.2 at 768, 38.7-38.9 at 640, 37.9-38.5 at
-    // 384 and 39.4-39.5 at 1024-1280 (profiles/r5_slots_sweep.txt); 768 with the in-launch reduction
-    // (profiles/r1_c2_pt_grid_sweep.txt)
-    slots = cus * (nb < 2 ? nb : 2);
-    const char* e = getenv("PCS_PT_SLOTS");  // diagnostics: grid-size sweep
-    if (e && atoi(e) > 0) slots = atoi(e);
-  }
-  return slots;
-}
-
-// tasks = 64-column strips x row segments of >= 4 steps, about one wave of resident blocks
-static bool pt_plan(const pcs_pds2d_args* a, RowBands rb, MarchPlan* p) {
-  const int tiles_x = (int)((a->n1 + PtGeom::TW - 1) / PtGeom::TW);
-  if (tiles_x < 2) return false;
-  plan_bands(rb, PtGeom::TS, tiles_x, pt_slots(), 4, p);
-  return true;
-}
-
-static bool use_pt(const pcs_pds2d_args* a) {
-  static int disabled = -1;  // PCS_NO_MARCH=1: diagnostics, force the tile kernel
-  if (disabled < 0) disabled = getenv("PCS_NO_MARCH") != nullptr;
-  if (disabled) return false;
-  if (a->dtype != PCS_F32 || !make_slab(a).vec) return false;
-  if (a->fkind != PCS_F_NULL && a->fkind != PCS_F_DENOISE && a->fkind != PCS_F_GRADBUF) return false;
-  if (a->hkind != PCS_H_L1 && a->hkind != PCS_H_L21) return false;
-  const int64_t hmax = a->halo_x > a->halo_z ? (a->halo_x > a->halo_y ? a->halo_x : a->halo_y)
-                                             : (a->halo_z > a->halo_y ? a->halo_z : a->halo_y);
-  if (!(a->n0 < (1LL << 30) && (a->rows + 2 * hmax) * a->n1 * 4 <= (1LL << 30))) return false;
-  MarchPlan p;
-  return pt_plan(a, full_bands(a), &p);
-}
-
-template <int FK, int HK>
-static int launch_pt(const pcs_pds2d_args* a, RowBands rb, hipStream_t st) {
-  MarchPlan p;
-  if (!pt_plan(a, rb, &p)) return PCS_EINVAL;
-  if (p.ntasks == 0) return PCS_OK;
-  const Slab s64 = make_slab(a);
-  const Slab32 s{(int)s64.n0, (int)s64.n1, (int)s64.row0, (int)s64.rows, s64.hx, s64.hy, s64.hz, s64.vec};
-  const Params<float> P = make_params<float>(a);
-  const float* g = FK == PCS_F_DENOISE ? (const float*)a->y : FK == PCS_F_GRADBUF ? (const float*)a->gbuf : nullptr;
-  k_pds2d_pt<FK, HK><<<(unsigned)p.ntasks + fin_extra(a, p.fin_n), 256, 0, st>>>((const float*)a->x, (float*)a->xn, (const float*)a->z,
-                                                         (float*)a->zn, g, s, P, a->gkind, a->partials,
-                                                         (Ctrl*)a->ctrl, a->hist, a->ws, red_out(a, p.fin_n), p.tiles_x, p.bd,
-                                                         p.ntasks);
-  return launch_status();
-}
-
-static int64_t bands_nblocks(const pcs_pds2d_args* a, RowBands rb);
-
-template <int FK>
-static int launch_pt(const pcs_pds2d_args* a, RowBands rb, hipStream_t st) {
-  return a->hkind == PCS_H_L21 ? launch_pt<FK, PCS_H_L21>(a, rb, st) : launch_pt<FK, PCS_H_L1>(a, rb, st);
-}
-
-// the row-marching families (march, pt, smarch) take row bands; the tile kernel runs whole slabs only
-static int pds2d_bands(const pcs_pds2d_args* a, RowBands rb, hipStream_t st) {
-  if (use_nm64(a)) return launch_nmarch64(a, rb, st);
-  if (use_smarch(a)) return a->dtype == PCS_F64 ? sm_launch<double>(a, rb, st) : sm_launch<float>(a, rb, st);
-  if (use_march(a)) return launch_march(a, rb, st);
-  if (a->kkind != PCS_K_GRAD_FORWARD) return PCS_EUNSUPPORTED;
-  if (a->fkind == PCS_F_DENOISE) return launch_pt<PCS_F_DENOISE>(a, rb, st);
-  if (a->fkind == PCS_F_GRADBUF) return launch_pt<PCS_F_GRADBUF>(a, rb, st);
-  return launch_pt<PCS_F_NULL>(a, rb, st);
-}
-
 template <typename T>
-static int pds2d(const pcs_pds2d_args* a, hipStream_t st) {
-  if (use_nm64(a) || use_smarch(a) || use_march(a)) return pds2d_bands(a, full_bands(a), st);
-  if (a->kkind != PCS_K_GRAD_FORWARD) return PCS_EUNSUPPORTED;
-  if (use_pt(a)) return pds2d_bands(a, full_bands(a), st);
+static int launch_tile(const pcs_pds2d_args* a, hipStream_t st) {
   switch (a->fkind) {
     case PCS_F_NULL: return launch_pds2d<T, PCS_F_NULL, 0>(a, st);
     case PCS_F_DENOISE: return launch_pds2d<T, PCS_F_DENOISE, 0>(a, st);
@@ -225,27 +142,63 @@ static int pds2d(const pcs_pds2d_args* a, hipStream_t st) {
   }
 }
 
-static int64_t bands_nblocks(const pcs_pds2d_args* a, RowBands rb) {
+// resident workgroups of the pointwise march (queried once)
+int pt_slots() {
+  static const int slots = [] {
+    const Occupancy o = occupancy(k_pds2d_pt<PCS_F_DENOISE, PCS_H_L21>, 256, 0, 4);
+    // 2 workgroups per CU (fewer, longer row segments) although 5 fit: C2 2048^2 with the deferred
+    // finalization 41.6-43.1 K it/s at 512 workgroups against 40.6-41.2 at 768, 38.7-38.9 at 640, 37.9-38.5 at
+    // 384 and 39.4-39.5 at 1024-1280 (profiles/r5_slots_sweep.txt); 768 with the in-launch reduction
+    // (profiles/r1_c2_pt_grid_sweep.txt)
+    return env_override("PCS_PT_SLOTS", o.cus * (o.per_cu < 2 ? o.per_cu : 2));
+  }();
+  return slots;
+}
+
+template <int FK, int HK>
+static int launch_pt(const pcs_pds2d_args* a, const MarchPlan& p, hipStream_t st) {
+  const Slab32 s = to_slab32(make_slab(a));
+  const Params<float> P = make_params<float>(a);
+  const float* g = FK == PCS_F_DENOISE ? (const float*)a->y : FK == PCS_F_GRADBUF ? (const float*)a->gbuf : nullptr;
+  k_pds2d_pt<FK, HK><<<(unsigned)p.ntasks + fin_extra(a, p.fin_n), 256, 0, st>>>(
+      (const float*)a->x, (float*)a->xn, (const float*)a->z, (float*)a->zn, g, s, P, a->gkind, a->partials,
+      (Ctrl*)a->ctrl, a->hist, a->ws, red_out(a, p.fin_n), p.tiles_x, p.bd, p.ntasks);
+  return launch_status();
+}
+
+template <int FK>
+static int launch_pt(const pcs_pds2d_args* a, const MarchPlan& p, hipStream_t st) {
+  return a->hkind == PCS_H_L21 ? launch_pt<FK, PCS_H_L21>(a, p, st) : launch_pt<FK, PCS_H_L1>(a, p, st);
+}
+
+static int launch_pt(const pcs_pds2d_args* a, const MarchPlan& p, hipStream_t st) {
+  if (p.ntasks == 0) return PCS_OK;
+  if (a->fkind == PCS_F_DENOISE) return launch_pt<PCS_F_DENOISE>(a, p, st);
+  if (a->fkind == PCS_F_GRADBUF) return launch_pt<PCS_F_GRADBUF>(a, p, st);
+  return launch_pt<PCS_F_NULL>(a, p, st);
+}
+
+// one launch of `path` (select_path; a family that takes bands) on the bands rb, planned by plan_for as p
+static int launch_for(int path, const pcs_pds2d_args* a, RowBands rb, const MarchPlan& p, hipStream_t st) {
+  switch (path) {
+    case PCS_PATH_NM64: return launch_nmarch64(a, p, st);
+    case PCS_PATH_SMARCH:
+    case PCS_PATH_SMARCH_NX:
+      return a->dtype == PCS_F64 ? sm_launch<double>(a, rb, p, st) : sm_launch<float>(a, rb, p, st);
+    case PCS_PATH_MARCH:
+    case PCS_PATH_NMARCH: return launch_march(a, path, p, st);
+    case PCS_PATH_PT: return launch_pt(a, p, st);
+    default: return PCS_EUNSUPPORTED;
+  }
+}
+
+// the step of checked arguments other than CONV2D's: the selector has planned the whole image
+static int pds2d(const pcs_pds2d_args* a, hipStream_t st) {
   MarchPlan p;
-  if (use_nm64(a)) {
-    nm64_plan(a, rb, &p);
-    return (int64_t)p.ntasks;
-  }
-  if (use_smarch(a)) {
-    sm_plan(a, rb, &p);
-    return (int64_t)p.ntasks;
-  }
-  if (use_march(a)) {
-    if (tier_for(a->half) == 3) march_plan<3>(a, rb, &p);
-    else march_plan<7>(a, rb, &p);
-    return (int64_t)p.ntasks;
-  }
-  if (a->kkind != PCS_K_GRAD_FORWARD) return -1;
-  if (use_pt(a)) {
-    pt_plan(a, rb, &p);
-    return (int64_t)p.ntasks;
-  }
-  return -1;
+  const int path = select_path(a, &p);
+  if (path == PCS_PATH_TILE) return a->dtype == PCS_F32 ? launch_tile<float>(a, st) : launch_tile<double>(a, st);
+  if (path < 0) return a->dtype == PCS_F32 || a->dtype == PCS_F64 ? PCS_EUNSUPPORTED : PCS_EINVAL;
+  return launch_for(path, a, full_bands(a), p, st);
 }
 
 static int needed_halo_x(int fkind, int half) {
@@ -295,8 +248,10 @@ int64_t pcs_pds2d_nblocks(const pcs_pds2d_args* a) {
     return pcs_pds2d_nblocks(&b);
   }
   if (!a || a->rows < 1 || a->n1 < 1) return -1;
-  if (use_nm64(a) || use_smarch(a) || a->kkind != PCS_K_GRAD_FORWARD) return bands_nblocks(a, full_bands(a));
-  if (use_march(a) || use_pt(a)) return bands_nblocks(a, full_bands(a));
+  MarchPlan p;
+  if (takes_bands(select_path(a, &p))) return (int64_t)p.ntasks;
+  if (a->kkind != PCS_K_GRAD_FORWARD) return -1;
+  // the tile grid (also of unchecked arguments that the step would refuse)
   const int th = a->dtype == PCS_F64 ? Tile<double>::TH : Tile<float>::TH;
   return ((a->n1 + 63) / 64) * ((a->rows + th - 1) / th);
 }
@@ -336,7 +291,7 @@ static int check_args(const pcs_pds2d_args* a) {
   if (a->fkind == PCS_F_SEPCONV && (!a->taps0 || !a->taps1 || a->half < 0)) return PCS_EINVAL;
   if (a->mkind != PCS_M_NONE) {  // the masked block: whole images, F = 0, the row march only
     if (a->mkind != PCS_M_L1LOSS || a->fkind != PCS_F_NULL || multi || !a->ym || !a->zm || !a->zmn) return PCS_EINVAL;
-    if (!use_smarch(a)) return PCS_EUNSUPPORTED;
+    if (select_path(a) != PCS_PATH_SMARCH) return PCS_EUNSUPPORTED;
   }
   const int hxn = needed_halo_x(a->fkind, a->half);
   if (hxn < 0) return PCS_EUNSUPPORTED;
@@ -353,7 +308,9 @@ static bool bands_ok(const pcs_pds2d_args* a, int64_t ra0, int64_t rb0, int64_t 
 
 int64_t pcs_pds2d_nblocks_bands(const pcs_pds2d_args* a, int64_t ra0, int64_t rb0, int64_t ra1, int64_t rb1) {
   if (check_args(a) != PCS_OK || !bands_ok(a, ra0, rb0, ra1, rb1)) return -1;
-  return bands_nblocks(a, RowBands{ra0, rb0, ra1, rb1});
+  MarchPlan p;
+  const int path = select_path(a);
+  return takes_bands(path) && plan_for(path, a, RowBands{ra0, rb0, ra1, rb1}, &p) ? (int64_t)p.ntasks : -1;
 }
 
 int pcs_pds2d_step_bands(const pcs_pds2d_args* a, int64_t ra0, int64_t rb0, int64_t ra1, int64_t rb1,
@@ -362,35 +319,22 @@ int pcs_pds2d_step_bands(const pcs_pds2d_args* a, int64_t ra0, int64_t rb0, int6
   if (rc != PCS_OK) return rc;
   if (a->hist || !bands_ok(a, ra0, rb0, ra1, rb1)) return PCS_EINVAL;
   if (a->fkind == PCS_F_CONV2D) return PCS_EUNSUPPORTED;  // its correlation passes run once per iteration
-  if (!(use_nm64(a) || use_smarch(a) || use_march(a) || (a->kkind == PCS_K_GRAD_FORWARD && use_pt(a))))
-    return PCS_EUNSUPPORTED;
-  return pds2d_bands(a, RowBands{ra0, rb0, ra1, rb1}, st);
-}
-
-int pcs_pds2d_supported(const pcs_pds2d_args* a) {
-  if (check_args(a) != PCS_OK) return 0;
-  if (a->fkind == PCS_F_CONV2D) {
-    const pcs_pds2d_args b = step_args(a);
-    return pcs_pds2d_supported(&b);
-  }
-  if (a->kkind != PCS_K_GRAD_FORWARD) return (use_nm64(a) || use_smarch(a) || use_march(a)) ? 1 : 0;
-  if (use_nm64(a) || use_smarch(a) || use_march(a) || use_pt(a)) return 1;
-  return (a->dtype == PCS_F32 || a->dtype == PCS_F64) && (a->fkind != PCS_F_SEPCONV || tier_for(a->half) > 0) ? 1 : 0;
+  const RowBands rb{ra0, rb0, ra1, rb1};
+  const int path = select_path(a);
+  if (!takes_bands(path)) return PCS_EUNSUPPORTED;
+  MarchPlan p;
+  if (!plan_for(path, a, rb, &p)) return PCS_EINVAL;
+  return launch_for(path, a, rb, p, st);
 }
 
 int pcs_pds2d_path(const pcs_pds2d_args* a) {
   if (check_args(a) != PCS_OK) return -1;
-  if (a->fkind == PCS_F_CONV2D) {
-    const pcs_pds2d_args b = step_args(a);
-    return pcs_pds2d_supported(&b) ? PCS_PATH_CONV2D : -1;
-  }
-  if (use_nm64(a)) return PCS_PATH_NM64;
-  if (use_smarch(a)) return a->fkind == PCS_F_SEPCONV ? PCS_PATH_SMARCH_NX : PCS_PATH_SMARCH;
-  if (use_march(a)) return use_nmarch(a) ? PCS_PATH_NMARCH : PCS_PATH_MARCH;
-  if (a->kkind != PCS_K_GRAD_FORWARD) return -1;
-  if (use_pt(a)) return PCS_PATH_PT;
-  return pcs_pds2d_supported(a) ? PCS_PATH_TILE : -1;
+  if (a->fkind != PCS_F_CONV2D) return select_path(a);
+  const pcs_pds2d_args b = step_args(a);
+  return check_args(&b) == PCS_OK && select_path(&b) >= 0 ? PCS_PATH_CONV2D : -1;
 }
+
+int pcs_pds2d_supported(const pcs_pds2d_args* a) { return pcs_pds2d_path(a) >= 0 ? 1 : 0; }
 
 int pcs_pds2d_step(const pcs_pds2d_args* a, hipStream_t st) {
   int rc = check_args(a);
@@ -401,9 +345,7 @@ int pcs_pds2d_step(const pcs_pds2d_args* a, hipStream_t st) {
     const pcs_pds2d_args b = step_args(a);
     return pcs_pds2d_step(&b, st);
   }
-  if (a->dtype == PCS_F32) return pds2d<float>(a, st);
-  if (a->dtype == PCS_F64) return pds2d<double>(a, st);
-  return PCS_EINVAL;
+  return pds2d(a, st);
 }
 
 // ---- the band-paired schedule of pcs_pds2d_run.  An iteration whose arrays exceed the Infinity Cache
@@ -425,15 +367,17 @@ constexpr int64_t kPairSetMin = 336LL << 20;   // bytes of the seven arrays, pro
 constexpr int64_t kPairHalfMax = 224LL << 20;  // bytes of the larger band's seven half-arrays, same file
 
 struct RunPlan {
-  bool paired;
-  int64_t m, nT, nB;  // split row (on the 16-row step grid), tasks (= partials) of T and of B
+  bool paired = false;
+  int64_t m = 0, nT = 0, nB = 0;  // split row (on the 16-row step grid), tasks (= partials) of T and of B
+  int path = -1;                  // the family of both band launches (select_path)
+  MarchPlan pT, pB;               // their plans (fin_n: set per launch)
 };
 
 // mode 0: one launch per iteration; 1: paired whenever the problem can run as two bands; 2: paired where the
 // size rule above says so; < 0: what PCS_RUN_BANDS says (0, 1 or auto = 2; read per call: the tests and the A/B
 // switch it), unset = 0 -- see the measurement above
 static RunPlan run_plan(const pcs_pds2d_args* a, int mode) {
-  RunPlan r{false, 0, 0, 0};
+  RunPlan r;
   if (mode < 0) {
     const char* e = getenv("PCS_RUN_BANDS");
     mode = e == nullptr || *e == '\0' ? 0 : strcmp(e, "auto") == 0 ? 2 : atoi(e);
@@ -442,17 +386,22 @@ static RunPlan run_plan(const pcs_pds2d_args* a, int mode) {
   // single images without a masked block; CONV2D's correlation passes and the stencil march's N x pass run
   // once per iteration on the whole image
   if (a->rows != a->n0 || a->mkind != PCS_M_NONE || a->fkind == PCS_F_CONV2D) return r;
-  if (use_smarch(a) && a->fkind == PCS_F_SEPCONV) return r;
-  if (!(use_nm64(a) || use_smarch(a) || use_march(a) || (a->kkind == PCS_K_GRAD_FORWARD && use_pt(a)))) return r;
+  r.path = select_path(a);
+  if (r.path == PCS_PATH_SMARCH_NX || !takes_bands(r.path)) return r;
+  // kept as it has always been: an fp64 problem on the fused march that could also run as the N x pass and the
+  // stencil march (sm_normal: it has a gradient buffer) stays on the single launch
+  if (r.path == PCS_PATH_NM64 && sm_normal(a)) return r;
   const int64_t m = (a->rows / 2 + 8) / 16 * 16;
   if (m <= 0 || m >= a->rows) return r;
   if (mode != 1) {
     const int64_t row = 7 * a->n1 * (a->dtype == PCS_F64 ? 8 : 4), big = m > a->rows - m ? m : a->rows - m;
     if (a->rows * row < kPairSetMin || big * row > kPairHalfMax) return r;
   }
-  const int64_t nT = bands_nblocks(a, RowBands{0, m, m, m}), nB = bands_nblocks(a, RowBands{m, a->rows, a->rows, a->rows});
-  if (nT < 1 || nB < 1) return r;
-  return RunPlan{true, m, nT, nB};
+  const RowBands top{0, m, m, m}, bottom{m, a->rows, a->rows, a->rows};
+  if (!plan_for(r.path, a, top, &r.pT) || !plan_for(r.path, a, bottom, &r.pB)) return r;
+  if (r.pT.ntasks < 1 || r.pB.ntasks < 1) return r;
+  r.paired = true, r.m = m, r.nT = r.pT.ntasks, r.nB = r.pB.ntasks;
+  return r;
 }
 
 // partials per iteration of pcs_pds2d_run in `mode` (run_plan): the combined count of the two band
@@ -487,7 +436,7 @@ int pcs_pds2d_run_plan(const pcs_pds2d_args* a, int mode, int64_t i, int64_t* ou
 // (pcs_pds2d_run_nblocks).
 int pcs_pds2d_run(const pcs_pds2d_args* a, int64_t n, hipStream_t st) {
   if (!a || n < 0 || !a->hist) return PCS_EINVAL;
-  const RunPlan rp = a->fin_partials ? run_plan(a, -1) : RunPlan{false, 0, 0, 0};
+  const RunPlan rp = a->fin_partials ? run_plan(a, -1) : RunPlan{};
   pcs_pds2d_args b = *a;
   for (int64_t i = 0; i < n; ++i) {
     if (i % 2) {
@@ -509,7 +458,9 @@ int pcs_pds2d_run(const pcs_pds2d_args* a, int64_t n, hipStream_t st) {
       const bool top = (k == 0) == (i % 2 == 0);
       const int64_t lo = top ? 0 : rp.m, hi = top ? rp.m : a->rows;
       b.partials = part + (top ? 0 : rp.nT * 4);
-      const int rc = pds2d_bands(&b, RowBands{lo, hi, hi, hi, k == 0 ? rp.nT + rp.nB : -1}, st);
+      MarchPlan p = top ? rp.pT : rp.pB;
+      p.fin_n = k == 0 ? rp.nT + rp.nB : -1;
+      const int rc = launch_for(rp.path, &b, RowBands{lo, hi, hi, hi}, p, st);
       if (rc != PCS_OK) return rc;
     }
   }

@@ -1,11 +1,15 @@
-// Host-side planning shared by the fused 2-D step's translation units (pds.hip: the ABI, loop control,
-// tile and pointwise-F kernels; pds_nm.hip: the separable-PSF row marches; pds_sm32.hip / pds_sm64.hip:
-// the general-stencil march per element type).  Kernels are instantiated only in the unit that launches
-// them, so the units compile in parallel.
+// Host-side planning shared by the fused 2-D step's translation units.  Everything that decides which kernel
+// family runs a call, and with which grid, is here: the families' predicates and planners, select_path (the
+// priority chain, evaluated in that one place) and plan_for.  The units hold the kernels' instantiations, their
+// occupancy queries and their launches, and receive the plan: pds.hip (the ABI, loop control, launch_for, the
+// tile and pointwise-F kernels), pds_nm.hip (the fp32 separable-PSF row marches), pds_sm32.hip / pds_sm64.hip
+// (the general-stencil march per element type), pds_nm64.hip (the fp64 normal-operator march).  Kernels are
+// instantiated only in the unit that launches them, so the units compile in parallel.
 #pragma once
 
 #include "pds_march.hpp"
 #include "pds_nmarch.hpp"
+#include "pds_pt.hpp"
 #include "pds_smarch.hpp"
 
 namespace pcs {
@@ -35,6 +39,16 @@ static Slab make_slab(const pcs_pds2d_args* a) {
   const int vec = (a->n1 % 4 == 0) && aligned16(a->x) && aligned16(a->xn) && aligned16(a->z) && aligned16(a->zn) &&
                   aligned16(a->y) && aligned16(a->gbuf);
   return Slab{a->n0, a->n1, a->row0, a->rows, a->halo_x, a->halo_y, a->halo_z, vec};
+}
+// the row marches index with 32 bits (fits_32bit_views)
+static Slab32 to_slab32(const Slab& s) {
+  return Slab32{(int)s.n0, (int)s.n1, (int)s.row0, (int)s.rows, s.hx, s.hy, s.hz, s.vec};
+}
+// 32-bit indexing, and every buffer view (the stored rows with the deepest halo; z: one per component) of at
+// most 2^30 bytes (common.hpp kOOB)
+static bool fits_32bit_views(const pcs_pds2d_args* a, int64_t elem_size) {
+  const int64_t hxz = a->halo_x > a->halo_z ? a->halo_x : a->halo_z, hmax = hxz > a->halo_y ? hxz : a->halo_y;
+  return a->n0 < (1LL << 30) && (a->rows + 2 * hmax) * a->n1 * elem_size <= (1LL << 30);
 }
 
 template <typename T>
@@ -110,13 +124,23 @@ static void plan_bands(RowBands rb, int TS, int tiles_x, int slots, int min_step
   p->ntasks = (int)(tiles_x * (n0 + n1));
 }
 
-// occupancy-derived grids of the kernels of other units (queried once each)
+// occupancy-derived grids of the units' kernels (queried once each)
+int pt_slots();                          // pds.hip: k_pds2d_pt
 int march_slots_h(int H);                // pds_nm.hip: k_pds2d_march, tiers 3 / 7
 int nmarch_slots_h(int H, bool gen);     // pds_nm.hip: k_pds2d_nmarch(_gen)
 template <typename T> int sm_slots();    // pds_sm32.hip / pds_sm64.hip: k_pds2d_smarch
-// launches of the other units
-int launch_march(const pcs_pds2d_args* a, RowBands rb, hipStream_t st);                      // pds_nm.hip
-template <typename T> int sm_launch(const pcs_pds2d_args* a, RowBands rb, hipStream_t st);  // pds_sm*.hip
+int nm64_slots();                        // pds_nm64.hip: k_pds2d_nmarch64
+// launches of the other units, with the plan of their bands (plan_for)
+int launch_march(const pcs_pds2d_args* a, int path, const MarchPlan& p, hipStream_t st);  // pds_nm.hip
+template <typename T>
+int sm_launch(const pcs_pds2d_args* a, RowBands rb, const MarchPlan& p, hipStream_t st);  // pds_sm*.hip
+int launch_nmarch64(const pcs_pds2d_args* a, const MarchPlan& p, hipStream_t st);         // pds_nm64.hip
+
+// PCS_NO_MARCH=1 (read once): diagnostics, force the tile kernel where a separable-PSF or pointwise march would run
+static bool march_disabled() {
+  static const bool disabled = getenv("PCS_NO_MARCH") != nullptr;
+  return disabled;
+}
 
 // the normal-operator march kernel (pds_nmarch.hpp): fp32 separable tiers 3 / 7 with the host's
 // Conv^T y and N tables; images of at least 64 x 64 (the edge bands of N never overlap).  Backward /
@@ -134,30 +158,43 @@ static bool use_nmarch(const pcs_pds2d_args* a) {
   return nmarch_gen_enabled() && last > tier_for(a->half);
 }
 
-template <int H>
-static bool march_plan(const pcs_pds2d_args* a, RowBands rb, MarchPlan* p) {
-  const bool nm = use_nmarch(a);
-  const int tw = nm ? NMarch<H>::TW : March<H>::TW;
-  const int tiles_x = (int)((a->n1 + tw - 1) / tw);
+// `nm`: the normal-operator march (use_nmarch), else the four-pass one; both tiers of both share the geometry
+static_assert(March<3>::TW == 64 && March<7>::TW == 64 && NMarch<3>::TW == 64 && NMarch<7>::TW == 64, "strip width");
+static_assert(March<3>::TS == 16 && March<7>::TS == 16 && NMarch<3>::TS == 16 && NMarch<7>::TS == 16, "step rows");
+static bool march_plan(const pcs_pds2d_args* a, RowBands rb, bool nm, MarchPlan* p) {
+  const int tiles_x = (int)((a->n1 + 63) / 64), H = tier_for(a->half);
   if (tiles_x < 2) return false;
-  plan_bands(rb, March<H>::TS, tiles_x, nm ? nmarch_slots_h(H, a->kkind != PCS_K_GRAD_FORWARD) : march_slots_h(H), 1, p);
+  plan_bands(rb, 16, tiles_x, nm ? nmarch_slots_h(H, a->kkind != PCS_K_GRAD_FORWARD) : march_slots_h(H), 1, p);
   return true;
 }
 
-static bool use_march(const pcs_pds2d_args* a) {
-  static int disabled = -1;  // PCS_NO_MARCH=1: diagnostics, force the tile kernel
-  if (disabled < 0) disabled = getenv("PCS_NO_MARCH") != nullptr;
-  if (disabled) return false;
+// `full`: the plan of the whole image; `nm`: which of the two marches
+static bool use_march(const pcs_pds2d_args* a, bool* nm, MarchPlan* full) {
+  if (march_disabled()) return false;
   const int t = tier_for(a->half);
   if (a->dtype != PCS_F32 || a->fkind != PCS_F_SEPCONV || (t != 3 && t != 7) || !make_slab(a).vec) return false;
   if (a->hkind != PCS_H_L1 && a->hkind != PCS_H_L21) return false;
-  if (a->kkind != PCS_K_GRAD_FORWARD && !use_nmarch(a)) return false;  // only the normal-operator march is general
-  const int64_t hmax = a->halo_x > a->halo_z ? (a->halo_x > a->halo_y ? a->halo_x : a->halo_y)
-                                             : (a->halo_z > a->halo_y ? a->halo_z : a->halo_y);
-  // 32-bit indexing and buffer views of at most 2^30 bytes (pds_march.hpp kOOB)
-  if (!(a->n0 < (1LL << 30) && (a->rows + 2 * hmax) * a->n1 * 4 <= (1LL << 30))) return false;
-  MarchPlan p;
-  return t == 3 ? march_plan<3>(a, full_bands(a), &p) : march_plan<7>(a, full_bands(a), &p);
+  *nm = use_nmarch(a);
+  if (a->kkind != PCS_K_GRAD_FORWARD && !*nm) return false;  // only the normal-operator march is general
+  return fits_32bit_views(a, 4) && march_plan(a, full_bands(a), *nm, full);
+}
+
+// ---- fp32 pointwise grad F (NULL / DENOISE / GRADBUF) with the forward Gradient: the row-marching kernel of
+// pds_pt.hpp.  Tasks = 64-column strips x row segments of >= 4 steps, about one wave of
+// resident blocks
+static bool pt_plan(const pcs_pds2d_args* a, RowBands rb, MarchPlan* p) {
+  const int tiles_x = (int)((a->n1 + PtGeom::TW - 1) / PtGeom::TW);
+  if (tiles_x < 2) return false;
+  plan_bands(rb, PtGeom::TS, tiles_x, pt_slots(), 4, p);
+  return true;
+}
+
+static bool use_pt(const pcs_pds2d_args* a, MarchPlan* full) {
+  if (march_disabled() || a->kkind != PCS_K_GRAD_FORWARD) return false;
+  if (a->dtype != PCS_F32 || !make_slab(a).vec) return false;
+  if (a->fkind != PCS_F_NULL && a->fkind != PCS_F_DENOISE && a->fkind != PCS_F_GRADBUF) return false;
+  if (a->hkind != PCS_H_L1 && a->hkind != PCS_H_L21) return false;
+  return fits_32bit_views(a, 4) && pt_plan(a, full_bands(a), full);
 }
 
 // ---- fp32 general-stencil K (backward / centred Gradient, Laplacian) with a pointwise grad F:
@@ -181,10 +218,8 @@ static int sm_slots_for(const pcs_pds2d_args* a) {
 // the fused fp64 normal-operator march (pds_nm64.hip): fp64, separable PSF of tier 3 / 7 with the host's
 // Conv^T y and fp64 N tables, Gradient K of any kind, H = lam L1 / L21; PCS_NM64=0 (read per call): the split
 // form (N x by k_sep2d_nrmm into the gradient buffer, then the stencil march)
-int nm64_slots();
 bool nm64_plan(const pcs_pds2d_args* a, RowBands rb, MarchPlan* p);
-int launch_nmarch64(const pcs_pds2d_args* a, RowBands rb, hipStream_t st);
-static bool use_nm64(const pcs_pds2d_args* a) {
+static bool use_nm64(const pcs_pds2d_args* a, MarchPlan* full) {
   const char* e = getenv("PCS_NM64");
   if (e != nullptr && atoi(e) == 0) return false;
   if (a->dtype != PCS_F64 || a->fkind != PCS_F_SEPCONV || a->mkind != PCS_M_NONE) return false;
@@ -198,11 +233,7 @@ static bool use_nm64(const pcs_pds2d_args* a) {
   if (a->rows < a->n0 &&
       (a->halo_x < 2 * t + 1 || a->halo_y < 1 || a->halo_z < (a->kkind == PCS_K_GRAD_FORWARD ? 1 : 2)))
     return false;
-  const int64_t hmax = a->halo_x > a->halo_z ? (a->halo_x > a->halo_y ? a->halo_x : a->halo_y)
-                                             : (a->halo_z > a->halo_y ? a->halo_z : a->halo_y);
-  if (!(a->n0 < (1LL << 30) && (a->rows + 2 * hmax) * a->n1 * 8 <= (1LL << 30))) return false;
-  MarchPlan p;
-  return nm64_plan(a, full_bands(a), &p);
+  return fits_32bit_views(a, 8) && nm64_plan(a, full_bands(a), full);
 }
 
 static bool sm_plan(const pcs_pds2d_args* a, RowBands rb, MarchPlan* p) {
@@ -278,10 +309,8 @@ int sep_normal_minus(int dt, const void* in, void* out, const void* sub, int64_t
 
 // fp64 (the reference's default dtype): every K kind, the forward Gradient included, takes this march
 // (the forward-only fp32 kernels pds_pt.hpp / pds_nmarch.hpp have no fp64 form)
-static bool use_smarch(const pcs_pds2d_args* a) {
+static bool use_smarch(const pcs_pds2d_args* a, MarchPlan* full) {
   if (a->kkind == PCS_K_GRAD_FORWARD && !sm_forward() && a->dtype != PCS_F64 && a->mkind == PCS_M_NONE) return false;
-  // separable PSF with backward / centred K: the fused normal-operator march (one launch) when it applies
-  if (a->kkind != PCS_K_GRAD_FORWARD && a->fkind == PCS_F_SEPCONV && use_march(a)) return false;
   if (a->kkind < PCS_K_GRAD_FORWARD || a->kkind > PCS_K_LAPLACIAN) return false;
   if ((a->dtype != PCS_F32 && a->dtype != PCS_F64) || !make_slab(a).vec) return false;
   if (a->fkind != PCS_F_NULL && a->fkind != PCS_F_DENOISE && a->fkind != PCS_F_GRADBUF &&
@@ -290,13 +319,54 @@ static bool use_smarch(const pcs_pds2d_args* a) {
   if (a->mkind != PCS_M_NONE && (a->fkind != PCS_F_NULL || !aligned16(a->ym) || !aligned16(a->zm) || !aligned16(a->zmn)))
     return false;
   if (a->hkind != PCS_H_L1 && (a->hkind != PCS_H_L21 || a->kkind == PCS_K_LAPLACIAN)) return false;
-  const int64_t hmax = a->halo_x > a->halo_z ? (a->halo_x > a->halo_y ? a->halo_x : a->halo_y)
-                                             : (a->halo_z > a->halo_y ? a->halo_z : a->halo_y);
-  const int64_t esz = a->dtype == PCS_F64 ? 8 : 4;
-  // 32-bit indexing; every buffer view (z: one per component) at most 2^30 bytes (kOOB)
-  if (!(a->n0 < (1LL << 30) && (a->rows + 2 * hmax) * a->n1 * esz <= (1LL << 30))) return false;
-  MarchPlan p;
-  return sm_plan(a, full_bands(a), &p);
+  return fits_32bit_views(a, a->dtype == PCS_F64 ? 8 : 4) && sm_plan(a, full_bands(a), full);
+}
+
+// ---- which family takes a call: the priority chain, first match wins
+//   1. PCS_PATH_NM64       fp64 separable PSF, the fused normal-operator march      (use_nm64)
+//   2. PCS_PATH_SMARCH(_NX) the general-stencil march, with its N x pass for a PSF   (use_smarch) -- but a
+//                          backward / centred K with a separable PSF takes 3 when it applies (one launch)
+//   3. PCS_PATH_(N)MARCH   fp32 separable PSF, tiers 3 / 7                           (use_march)
+//   the families below take the forward Gradient only
+//   4. PCS_PATH_PT        fp32 pointwise grad F                                     (use_pt)
+//   5. PCS_PATH_TILE       fp32 / fp64, any PSF tier
+// Returns the PCS_PATH_* value or -1; for 1-4, `full` (when given) holds the plan of the whole image.  A
+// CONV2D call is its correlation passes and the GRADBUF step: callers ask about the latter (step_args).  A
+// masked block runs on PCS_PATH_SMARCH alone: check_args (pds.hip) refuses it when this gives anything else.
+static int select_path(const pcs_pds2d_args* a, MarchPlan* full = nullptr) {
+  MarchPlan own, pm;
+  if (full == nullptr) full = &own;
+  *full = MarchPlan{};
+  bool nm = false;
+  const bool march = use_march(a, &nm, &pm);
+  if (use_nm64(a, full)) return PCS_PATH_NM64;
+  if (!(march && a->kkind != PCS_K_GRAD_FORWARD) && use_smarch(a, full))
+    return a->fkind == PCS_F_SEPCONV ? PCS_PATH_SMARCH_NX : PCS_PATH_SMARCH;
+  if (march) {
+    *full = pm;
+    return nm ? PCS_PATH_NMARCH : PCS_PATH_MARCH;
+  }
+  if (use_pt(a, full)) return PCS_PATH_PT;
+  const bool tile = a->kkind == PCS_K_GRAD_FORWARD && (a->dtype == PCS_F32 || a->dtype == PCS_F64) &&
+                    (a->fkind != PCS_F_SEPCONV || tier_for(a->half) > 0);
+  return tile ? PCS_PATH_TILE : -1;
+}
+
+// the row-marching families take row bands; the tile kernel runs whole slabs only
+static bool takes_bands(int path) { return path > 0 && path != PCS_PATH_TILE; }
+
+// the plan of a launch of `path` (one that takes bands) on the bands rb
+static bool plan_for(int path, const pcs_pds2d_args* a, RowBands rb, MarchPlan* p) {
+  *p = MarchPlan{};
+  switch (path) {
+    case PCS_PATH_NM64: return nm64_plan(a, rb, p);
+    case PCS_PATH_SMARCH:
+    case PCS_PATH_SMARCH_NX: return sm_plan(a, rb, p);
+    case PCS_PATH_MARCH:
+    case PCS_PATH_NMARCH: return march_plan(a, rb, path == PCS_PATH_NMARCH, p);
+    case PCS_PATH_PT: return pt_plan(a, rb, p);
+    default: return false;
+  }
 }
 
 }  // namespace pcs

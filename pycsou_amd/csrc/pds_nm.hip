@@ -8,89 +8,68 @@ namespace pcs {
 // resident workgroups of the march kernel on the whole device (queried once)
 template <int H>
 static int march_slots() {
-  static int slots = 0;
-  if (slots == 0) {
-    int dev = 0, cus = 0, nb = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                hipSuccess || cus < 1)
-      cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_pds2d_march<float, H, PCS_H_L21, kMarchNT>, kMarchNT,
-                                                     0) != hipSuccess ||
-        nb < 1)
-      nb = 3;
-    (void)hipGetLastError();
-    slots = cus * nb;
-  }
+  static const int slots = [] {
+    const Occupancy o = occupancy(k_pds2d_march<float, H, PCS_H_L21, kMarchNT>, kMarchNT, 0, 3);
+    return o.cus * o.per_cu;
+  }();
   return slots;
 }
 
-template <int H>
-static int nmarch_slots(bool gen) {
-  static int slots_f = 0, slots_g = 0;
-  int& slots = gen ? slots_g : slots_f;
-  if (slots == 0) {
-    int dev = 0, cus = 0, nb = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                hipSuccess || cus < 1)
-      cus = 256;
-    const hipError_t oe =
-        gen ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                  &nb, k_pds2d_nmarch_gen<float, H, PCS_H_L21, kNMarchNT, PCS_CENTERED>, kNMarchNT, 0)
-            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_pds2d_nmarch<float, H, PCS_H_L21, kNMarchNT>,
-                                                           kNMarchNT, 0);
-    if (oe != hipSuccess ||
-        nb < 1)
-      nb = 3;
-    (void)hipGetLastError();
-    slots = cus * nb;
-    const char* e = getenv("PCS_NMARCH_SLOTS");  // diagnostics: grid-size sweep
-    if (e && atoi(e) > 0) slots = atoi(e);
-  }
+template <int H, bool GEN>
+static int nmarch_slots() {
+  static const int slots = [] {
+    const Occupancy o = GEN ? occupancy(k_pds2d_nmarch_gen<float, H, PCS_H_L21, kNMarchNT, PCS_CENTERED>, kNMarchNT, 0, 3)
+                            : occupancy(k_pds2d_nmarch<float, H, PCS_H_L21, kNMarchNT>, kNMarchNT, 0, 3);
+    return env_override("PCS_NMARCH_SLOTS", o.cus * o.per_cu);
+  }();
   return slots;
 }
 
 int march_slots_h(int H) { return H == 3 ? march_slots<3>() : march_slots<7>(); }
-int nmarch_slots_h(int H, bool gen) { return H == 3 ? nmarch_slots<3>(gen) : nmarch_slots<7>(gen); }
+int nmarch_slots_h(int H, bool gen) {
+  if (gen) return H == 3 ? nmarch_slots<3, true>() : nmarch_slots<7, true>();
+  return H == 3 ? nmarch_slots<3, false>() : nmarch_slots<7, false>();
+}
+
+enum MarchKernel { kFourPass, kNormalFwd, kNormalGen };  // k_pds2d_march, k_pds2d_nmarch, k_pds2d_nmarch_gen
 
 template <int H, int HK>
-static int launch_march_k(const pcs_pds2d_args* a, RowBands rb, hipStream_t st) {
-  MarchPlan p;
-  if (!march_plan<H>(a, rb, &p)) return PCS_EINVAL;
-  if (p.ntasks == 0) return PCS_OK;
-  const Slab s64 = make_slab(a);
-  const Slab32 s{(int)s64.n0, (int)s64.n1, (int)s64.row0, (int)s64.rows, s64.hx, s64.hy, s64.hz, s64.vec};
+static int launch_march_k(const pcs_pds2d_args* a, MarchKernel which, const MarchPlan& p, hipStream_t st) {
+  const Slab32 s = to_slab32(make_slab(a));
   const Params<float> P = make_params<float>(a);
-  if (use_nmarch(a) && a->kkind != PCS_K_GRAD_FORWARD) {
+  const unsigned grid = (unsigned)p.ntasks + fin_extra(a, p.fin_n);
+  if (which == kNormalGen) {
     auto kern = a->kkind == PCS_K_GRAD_BACKWARD ? k_pds2d_nmarch_gen<float, H, HK, kNMarchNT, PCS_BACKWARD>
                                                 : k_pds2d_nmarch_gen<float, H, HK, kNMarchNT, PCS_CENTERED>;
-    kern<<<(unsigned)p.ntasks + fin_extra(a, p.fin_n), kNMarchNT, 0, st>>>((const float*)a->x, (float*)a->xn, (const float*)a->z, (float*)a->zn,
-                                                   (const float*)a->cty, (const float*)a->ntaps, s, P, a->gkind,
-                                                   a->edge, a->partials, (Ctrl*)a->ctrl, a->hist, a->ws, red_out(a, p.fin_n),
-                                                   p.tiles_x, p.bd, p.ntasks);
-    return launch_status();
-  }
-  if (use_nmarch(a)) {
-    k_pds2d_nmarch<float, H, HK, kNMarchNT><<<(unsigned)p.ntasks + fin_extra(a, p.fin_n), kNMarchNT, 0, st>>>(
+    kern<<<grid, kNMarchNT, 0, st>>>((const float*)a->x, (float*)a->xn, (const float*)a->z, (float*)a->zn,
+                                     (const float*)a->cty, (const float*)a->ntaps, s, P, a->gkind, a->edge,
+                                     a->partials, (Ctrl*)a->ctrl, a->hist, a->ws, red_out(a, p.fin_n), p.tiles_x, p.bd,
+                                     p.ntasks);
+  } else if (which == kNormalFwd) {
+    k_pds2d_nmarch<float, H, HK, kNMarchNT><<<grid, kNMarchNT, 0, st>>>(
         (const float*)a->x, (float*)a->xn, (const float*)a->z, (float*)a->zn, (const float*)a->cty,
-        (const float*)a->ntaps, s, P, a->gkind, a->partials, (Ctrl*)a->ctrl, a->hist, a->ws, red_out(a, p.fin_n), p.tiles_x,
-        p.bd, p.ntasks);
-    return launch_status();
+        (const float*)a->ntaps, s, P, a->gkind, a->partials, (Ctrl*)a->ctrl, a->hist, a->ws, red_out(a, p.fin_n),
+        p.tiles_x, p.bd, p.ntasks);
+  } else {
+    k_pds2d_march<float, H, HK, kMarchNT><<<grid, kMarchNT, 0, st>>>(
+        (const float*)a->x, (float*)a->xn, (const float*)a->z, (float*)a->zn, (const float*)a->y,
+        (const float*)a->taps0, (const float*)a->taps1, a->half, s, P, a->gkind, a->partials, (Ctrl*)a->ctrl, a->hist,
+        a->ws, red_out(a, p.fin_n), p.tiles_x, p.bd, p.ntasks);
   }
-  if (a->kkind != PCS_K_GRAD_FORWARD) return PCS_EUNSUPPORTED;
-  k_pds2d_march<float, H, HK, kMarchNT><<<(unsigned)p.ntasks + fin_extra(a, p.fin_n), kMarchNT, 0, st>>>(
-      (const float*)a->x, (float*)a->xn, (const float*)a->z, (float*)a->zn, (const float*)a->y,
-      (const float*)a->taps0, (const float*)a->taps1, a->half, s, P, a->gkind, a->partials, (Ctrl*)a->ctrl, a->hist,
-      a->ws, red_out(a, p.fin_n), p.tiles_x, p.bd, p.ntasks);
   return launch_status();
 }
 
 template <int H>
-static int launch_march_k(const pcs_pds2d_args* a, RowBands rb, hipStream_t st) {
-  return a->hkind == PCS_H_L21 ? launch_march_k<H, PCS_H_L21>(a, rb, st) : launch_march_k<H, PCS_H_L1>(a, rb, st);
+static int launch_march_k(const pcs_pds2d_args* a, MarchKernel which, const MarchPlan& p, hipStream_t st) {
+  return a->hkind == PCS_H_L21 ? launch_march_k<H, PCS_H_L21>(a, which, p, st)
+                               : launch_march_k<H, PCS_H_L1>(a, which, p, st);
 }
 
-int launch_march(const pcs_pds2d_args* a, RowBands rb, hipStream_t st) {
-  return tier_for(a->half) == 3 ? launch_march_k<3>(a, rb, st) : launch_march_k<7>(a, rb, st);
+// path: PCS_PATH_MARCH (forward K) or PCS_PATH_NMARCH (select_path)
+int launch_march(const pcs_pds2d_args* a, int path, const MarchPlan& p, hipStream_t st) {
+  if (p.ntasks == 0) return PCS_OK;
+  const MarchKernel which = path == PCS_PATH_MARCH ? kFourPass : a->kkind == PCS_K_GRAD_FORWARD ? kNormalFwd : kNormalGen;
+  return tier_for(a->half) == 3 ? launch_march_k<3>(a, which, p, st) : launch_march_k<7>(a, which, p, st);
 }
 
 }  // namespace pcs

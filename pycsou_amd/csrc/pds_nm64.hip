@@ -495,22 +495,12 @@ static void nm64_attr() {
 
 // resident workgroups of the kernel on the device (one per CU at 141 KB of LDS; queried once)
 int nm64_slots() {
-  static int slots = 0;
-  if (slots == 0) {
-    int dev = 0, cus = 0, nb = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                hipSuccess || cus < 1)
-      cus = 256;
+  static const int slots = [] {
     nm64_attr<7, PCS_H_L21, PCS_CENTERED>();
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_pds2d_nmarch64<7, PCS_H_L21, PCS_CENTERED>, 512,
-                                                     NM64<7>::SZ * sizeof(double)) != hipSuccess ||
-        nb < 1)
-      nb = 1;
-    (void)hipGetLastError();
-    slots = cus * nb;
-    const char* e = getenv("PCS_NM64_SLOTS");  // diagnostics: grid-size sweep
-    if (e && atoi(e) > 0) slots = atoi(e);
-  }
+    const Occupancy o =
+        occupancy(k_pds2d_nmarch64<7, PCS_H_L21, PCS_CENTERED>, 512, NM64<7>::SZ * sizeof(double), 1);
+    return env_override("PCS_NM64_SLOTS", o.cus * o.per_cu);
+  }();
   return slots;
 }
 
@@ -545,8 +535,7 @@ bool nm64_plan(const pcs_pds2d_args* a, RowBands rb, MarchPlan* p) {
 
 template <int H, int HK, int KK>
 static int nm64_go(const pcs_pds2d_args* a, const MarchPlan& p, hipStream_t st) {
-  const Slab s64 = make_slab(a);
-  const Slab32 s{(int)s64.n0, (int)s64.n1, (int)s64.row0, (int)s64.rows, s64.hx, s64.hy, s64.hz, s64.vec};
+  const Slab32 s = to_slab32(make_slab(a));
   const Params<double> P = make_params<double>(a);
   nm64_attr<H, HK, KK>();
   k_pds2d_nmarch64<H, HK, KK><<<(unsigned)p.ntasks + fin_extra(a, p.fin_n), 512, NM64<H>::SZ * sizeof(double), st>>>(
@@ -566,9 +555,7 @@ static int nm64_k(const pcs_pds2d_args* a, const MarchPlan& p, hipStream_t st) {
   }
 }
 
-int launch_nmarch64(const pcs_pds2d_args* a, RowBands rb, hipStream_t st) {
-  MarchPlan p;
-  if (!nm64_plan(a, rb, &p)) return PCS_EINVAL;
+int launch_nmarch64(const pcs_pds2d_args* a, const MarchPlan& p, hipStream_t st) {
   if (p.ntasks == 0) return PCS_OK;
   const bool l21 = a->hkind == PCS_H_L21;
   if (tier_for(a->half) == 3) return l21 ? nm64_k<3, PCS_H_L21>(a, p, st) : nm64_k<3, PCS_H_L1>(a, p, st);

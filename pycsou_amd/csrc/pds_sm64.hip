@@ -3,5 +3,5 @@
 
 namespace pcs {
 template int sm_slots<double>();
-template int sm_launch<double>(const pcs_pds2d_args* a, RowBands rb, hipStream_t st);
+template int sm_launch<double>(const pcs_pds2d_args* a, RowBands rb, const MarchPlan& p, hipStream_t st);
 }  // namespace pcs

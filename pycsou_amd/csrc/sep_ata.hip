@@ -284,21 +284,11 @@ static void ata_attr() {
 // resident workgroups of k_sep2d_ata<T> on the device (queried once per type)
 template <typename T>
 static int ata_slots() {
-  static int slots = 0;
-  if (slots == 0) {
-    int dev = 0, cus = 0, nb = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                hipSuccess || cus < 1)
-      cus = 256;
-    const size_t lds = ata_lds_bytes<T>();
+  static const int slots = [] {
     ata_attr<T, 1>();
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_sep2d_ata<T, 1>, AtaG::NT, lds) != hipSuccess || nb < 1)
-      nb = 1;
-    (void)hipGetLastError();
-    slots = cus * nb;
-    const char* e = getenv("PCS_ATA_SLOTS");  // diagnostics: grid-size sweep
-    if (e && atoi(e) > 0) slots = atoi(e);
-  }
+    const Occupancy o = occupancy(k_sep2d_ata<T, 1>, AtaG::NT, ata_lds_bytes<T>(), 1);
+    return env_override("PCS_ATA_SLOTS", o.cus * o.per_cu);
+  }();
   return slots;
 }
 
@@ -334,21 +324,11 @@ static void nrm_attr() {
 
 template <typename T>
 static int nrm_slots() {
-  static int slots = 0;
-  if (slots == 0) {
-    int dev = 0, cus = 0, nb = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                hipSuccess || cus < 1)
-      cus = 256;
+  static const int slots = [] {
     nrm_attr<T, false>();
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nrm_fn<T, false>(), 256, nrm_lds<T>()) != hipSuccess ||
-        nb < 1)
-      nb = 1;
-    (void)hipGetLastError();
-    slots = cus * nb;
-    const char* e = getenv("PCS_ATA_SLOTS");  // diagnostics: grid-size sweep
-    if (e && atoi(e) > 0) slots = atoi(e);
-  }
+    const Occupancy o = occupancy(nrm_fn<T, false>(), 256, nrm_lds<T>(), 1);
+    return env_override("PCS_ATA_SLOTS", o.cus * o.per_cu);
+  }();
   return slots;
 }
 
