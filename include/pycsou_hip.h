@@ -195,6 +195,47 @@ int pcs_prox_sql2(int dtype, const void* x, void* out, int64_t n, double tau, hi
 /* NonNegativeOrthant / Segment projections (math/prox.py:295-297, 340-343). */
 int pcs_proj_nonneg(int dtype, const void* x, void* out, int64_t n, hipStream_t stream);
 int pcs_proj_segment(int dtype, const void* x, void* out, int64_t n, double a, double b, hipStream_t stream);
+/* KLDivergence.prox (pycsou/func/loss.py:682): out = (d + sqrt(d^2 + 4 tau y)) / 2, d = x - tau; for d < 0
+ * the same root as 2 tau y / (sqrt(.) - d), which does not cancel -- more accurate than the reference
+ * there, and exactly 0 for y = 0, d <= 0 as in the reference.  fp64 arithmetic for both dtypes; tau > 0. */
+int pcs_prox_kl(int dtype, const void* x, const void* y, void* out, int64_t n, double tau, hipStream_t stream);
+/* LogBarrier.prox (func/penalty.py:840): out = (x + sqrt(x^2 + 4 tau)) / 2, for x < 0 as
+ * 2 tau / (sqrt(.) - x) (more accurate than the reference there).  tau > 0. */
+int pcs_prox_logbarrier(int dtype, const void* x, void* out, int64_t n, double tau, hipStream_t stream);
+/* ShannonEntropy.prox (func/penalty.py:921-922): out = tau W0(exp(x / tau - 1) / tau), evaluated in the log
+ * domain: out = tau w with w + ln w = x / tau - 1 - ln tau.  Underflows to 0 like the reference for very
+ * negative x / tau.  Deliberate deviation: stays finite where the reference's exp overflows to inf
+ * (x / tau >~ 709).  tau > 0. */
+int pcs_prox_entropy(int dtype, const void* x, void* out, int64_t n, double tau, hipStream_t stream);
+
+/* One global threshold (pycsou/math/prox.py:158-164 proj_l1_ball, func/base.py:239-240 with it for
+ * LInftyNorm.prox, func/penalty.py:296-316 SquaredL1Norm.prox; the reference searches on the host with
+ * brentq or a full sort):
+ *   t = 0 if sum |x_i| <= a, else the root t > 0 of sum max(|x_i| - t, 0) = a + b t
+ *   (a >= 0, b >= 0, not both 0), i.e. t = (S_k - a) / (k + b) over the k elements above the crossing;
+ *   mode PCS_THRESH_SOFT: out = sign(x) max(|x| - t, 0)   (t = 0: a bitwise copy of x)
+ *   mode PCS_THRESH_CLIP: out = clip(x, -t, t)            (t = 0: zeros)
+ * L1Ball(r).prox: a = r, b = 0, SOFT.  LInftyNorm.prox(x, tau): a = tau, b = 0, CLIP.
+ * SquaredL1Norm.prox(x, tau): a = 0, b = 1 / (2 tau), SOFT (the 'sort' threshold 2 tau / (1 + 2 tau k) S_k).
+ * The crossing is located exactly, by 32-section of the ordered bit patterns of |x| down to two adjacent
+ * representable values (7 passes fp32, 13 fp64), not to a tolerance in value; all sums are fp64 in a fixed
+ * order, so two calls agree bitwise.  19 (fp32) / 31 (fp64) plain launches whatever the data, no host
+ * read-back, no atomics: capturable in a hipGraph.  t_dev (device double, may be NULL) receives t.
+ * ws >= pcs_thresh_ws_bytes(n), 8-byte aligned.  x == out is allowed.  Arguments are checked before any
+ * device call; n = 0 is a no-op. */
+enum { PCS_THRESH_SOFT = 0, PCS_THRESH_CLIP = 1 };
+#define PCS_THRESH_PIVOTS 31
+int64_t pcs_thresh_ws_bytes(int64_t n);
+int pcs_thresh_l1(int dtype, const void* x, void* out, int64_t n, double a, double b, int mode, double* t_dev,
+                  void* ws, hipStream_t stream);
+/* Host-only: one bracket selection of pcs_thresh_l1's stage 2 (the same __host__ __device__ code).  The
+ * bracket [lo, hi] of keys (bit patterns of |x| in `dtype`) has pivots j = 1 .. PCS_THRESH_PIVOTS at
+ * lo + j ceil((hi - lo) / 32), clamped to hi; pivots_out (may be NULL) receives their values.  With
+ * sums[j - 1] = sum max(|x| - pivot_j, 0): returns 0 and bracket_out = {0, 0} if sum_abs <= a (t = 0),
+ * else PCS_THRESH_PIVOTS and bracket_out = {pivot k - 1, pivot k}, k the first pivot with
+ * sums - a - b pivot <= 0 (pivot 0 = lo, pivot 32 = hi).  sums == NULL: pivots only. */
+int pcs_thresh_pick_host(int dtype, uint64_t lo, uint64_t hi, double sum_abs, const double* sums, double a,
+                         double b, double* pivots_out, uint64_t* bracket_out);
 
 /* ---------------------------------------------------------------- algebra / reductions */
 

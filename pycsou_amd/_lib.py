@@ -20,6 +20,8 @@ PCS_H_L1, PCS_H_L21 = 0, 1
 PCS_K_GRAD_FORWARD, PCS_K_GRAD_BACKWARD, PCS_K_GRAD_CENTERED, PCS_K_LAPLACIAN = 0, 1, 2, 3
 PCS_G_NULL, PCS_G_NONNEG, PCS_G_SEGMENT = 0, 1, 2
 PCS_APGD_G_L1 = 3
+PCS_THRESH_SOFT, PCS_THRESH_CLIP = 0, 1
+PCS_THRESH_PIVOTS = 31
 PCS_F_NULL, PCS_F_DENOISE, PCS_F_SEPCONV, PCS_F_GRADBUF, PCS_F_CONV2D, PCS_F_CONV0 = 0, 1, 2, 3, 4, 5
 PCS_M_NONE, PCS_M_L1LOSS = 0, 1
 # pcs_pds2d_path: the kernel family of a fused 2-D step
@@ -139,6 +141,13 @@ _SIGS = {
     'pcs_prox_sql2': (_c_int, [_c_int, _vp, _vp, _c_i64, _c_dbl, _vp]),
     'pcs_proj_nonneg': (_c_int, [_c_int, _vp, _vp, _c_i64, _vp]),
     'pcs_proj_segment': (_c_int, [_c_int, _vp, _vp, _c_i64, _c_dbl, _c_dbl, _vp]),
+    'pcs_prox_kl': (_c_int, [_c_int, _vp, _vp, _vp, _c_i64, _c_dbl, _vp]),
+    'pcs_prox_logbarrier': (_c_int, [_c_int, _vp, _vp, _c_i64, _c_dbl, _vp]),
+    'pcs_prox_entropy': (_c_int, [_c_int, _vp, _vp, _c_i64, _c_dbl, _vp]),
+    'pcs_thresh_ws_bytes': (_c_i64, [_c_i64]),
+    'pcs_thresh_l1': (_c_int, [_c_int, _vp, _vp, _c_i64, _c_dbl, _c_dbl, _c_int, _vp, _vp, _vp]),
+    'pcs_thresh_pick_host': (_c_int, [_c_int, ctypes.c_uint64, ctypes.c_uint64, _c_dbl, _pdbl, _c_dbl, _c_dbl, _pdbl,
+                                      ctypes.POINTER(ctypes.c_uint64)]),
     'pcs_axpby': (_c_int, [_c_int, _vp, _vp, _vp, _c_i64, _c_dbl, _c_dbl, _vp]),
     'pcs_mul': (_c_int, [_c_int, _vp, _vp, _vp, _c_i64, _vp]),
     'pcs_rel_sums': (_c_int, [_c_int, _vp, _vp, _c_i64, _vp, _vp, _vp]),

@@ -241,6 +241,54 @@ def proj_segment(x, a, b):
     return out
 
 
+def _thresh_ws(t):
+    """Workspace of pcs_thresh_l1 (its size does not grow past the kernel's block cap), cached per device
+    like ``_ws`` so that a captured loop replays with the buffer it was captured with."""
+    key = (t.device, 'thresh')
+    ws = _ws_cache.get(key)
+    if ws is None:
+        lib = L.gpu()
+        ws = torch.empty(int(lib.pcs_thresh_ws_bytes(1 << 40)) // 8 + 8, dtype=torch.float64, device=t.device)
+        _ws_cache[key] = ws
+    return ws
+
+
+def thresh_l1(x, a, b, mode, t_out=None):
+    """One global threshold (``pcs_thresh_l1``): ``t = 0`` if ``sum|x| <= a``, else the root of
+    ``sum max(|x| - t, 0) = a + b t``; mode 'soft' -> ``sign(x) max(|x| - t, 0)``, 'clip' ->
+    ``clip(x, -t, t)``.  ``t_out``: a 1-element float64 device tensor that receives t.  No host sync."""
+    lib = L.gpu()
+    out = torch.empty_like(x)
+    code = {'soft': L.PCS_THRESH_SOFT, 'clip': L.PCS_THRESH_CLIP}[mode]
+    L.check(lib.pcs_thresh_l1(L.dtcode(x), L.ptr(x), L.ptr(out), x.numel(), float(a), float(b), code, L.ptr(t_out),
+                              L.ptr(_thresh_ws(x)), L.stream()), 'pcs_thresh_l1')
+    return out
+
+
+def prox_kl(x, y, tau):
+    lib = L.gpu()
+    out = torch.empty_like(x)
+    L.check(lib.pcs_prox_kl(L.dtcode(x), L.ptr(x), L.ptr(y), L.ptr(out), x.numel(), float(tau), L.stream()),
+            'pcs_prox_kl')
+    return out
+
+
+def prox_logbarrier(x, tau):
+    lib = L.gpu()
+    out = torch.empty_like(x)
+    L.check(lib.pcs_prox_logbarrier(L.dtcode(x), L.ptr(x), L.ptr(out), x.numel(), float(tau), L.stream()),
+            'pcs_prox_logbarrier')
+    return out
+
+
+def prox_entropy(x, tau):
+    lib = L.gpu()
+    out = torch.empty_like(x)
+    L.check(lib.pcs_prox_entropy(L.dtcode(x), L.ptr(x), L.ptr(out), x.numel(), float(tau), L.stream()),
+            'pcs_prox_entropy')
+    return out
+
+
 # ---------------------------------------------------------------- operators
 
 def grad_fwd(x, dims, steps, kind, edge):

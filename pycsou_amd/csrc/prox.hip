@@ -176,6 +176,50 @@ __global__ void k_mul(const T* __restrict__ x, const T* __restrict__ d, T* __res
   PCS_GRID_LOOP(p, n) out[p] = d[p] * x[p];
 }
 
+// positive root of u^2 - d u - c = 0 (c >= 0): (d + sqrt(d^2 + 4c)) / 2, taken as 2c / (sqrt(.) - d) when
+// d < 0 so that nothing cancels; exactly 0 for c = 0, d <= 0.  fp64 arithmetic for both dtypes.
+__device__ __forceinline__ double pos_root(double d, double c) {
+  const double s = sqrt(d * d + 4.0 * c);
+  return d >= 0.0 ? 0.5 * (d + s) : (2.0 * c) / (s - d);
+}
+
+template <typename T>
+__global__ void k_prox_kl(const T* __restrict__ x, const T* __restrict__ y, T* __restrict__ out, int64_t n,
+                          double tau) {
+  // loss.py:682: (x - tau + sqrt((x - tau)^2 + 4 tau y)) / 2
+  PCS_GRID_LOOP(p, n) out[p] = (T)pos_root((double)x[p] - tau, tau * (double)y[p]);
+}
+
+template <typename T>
+__global__ void k_prox_logbarrier(const T* __restrict__ x, T* __restrict__ out, int64_t n, double tau) {
+  // penalty.py:840: (x + sqrt(x^2 + 4 tau)) / 2
+  PCS_GRID_LOOP(p, n) out[p] = (T)pos_root((double)x[p], tau);
+}
+
+// w > 0 with w + ln w = l, i.e. W0(e^l).  l <= 1: Newton on w e^w = e^l from e^l / (1 + e^l) (below the
+// root; e^l underflows to w = 0); l > 1: Newton on w + ln w = l from l - ln l (below the root, where the
+// concave map keeps the iterates), which never forms e^l.  Both converge quadratically from a start within
+// 0.4 of the root: six steps reach fp64 rounding.
+__device__ __forceinline__ double lambert_log(double l) {
+  if (l <= 1.0) {
+    const double u = exp(l);
+    double w = u / (1.0 + u);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) w -= (w - u * exp(-w)) / (1.0 + w);
+    return w;
+  }
+  double w = l - log(l);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) w = w * (1.0 + l - log(w)) / (1.0 + w);
+  return w;
+}
+
+template <typename T>
+__global__ void k_prox_entropy(const T* __restrict__ x, T* __restrict__ out, int64_t n, double tau, double ltau) {
+  // penalty.py:921-922: tau W0(exp(x / tau - 1) / tau)
+  PCS_GRID_LOOP(p, n) out[p] = (T)(tau * lambert_log((double)x[p] / tau - 1.0 - ltau));
+}
+
 constexpr int kRedBlocks = 1024;
 
 // both sums of one relative improvement in one pass: part[b] = (sum (a-b)^2, sum a^2) of block b
@@ -394,6 +438,27 @@ int pcs_proj_nonneg(int dt, const void* x, void* out, int64_t n, hipStream_t st)
 int pcs_proj_segment(int dt, const void* x, void* out, int64_t n, double a, double b, hipStream_t st) {
   if (!x || !out || n < 0) return PCS_EINVAL;
   PCS_DISPATCH(dt, k_proj_segment<T><<<grid_for(n, 256), 256, 0, st>>>((const T*)x, (T*)out, n, (T)a, (T)b));
+  return launch_status();
+}
+
+int pcs_prox_kl(int dt, const void* x, const void* y, void* out, int64_t n, double tau, hipStream_t st) {
+  if ((dt != PCS_F32 && dt != PCS_F64) || !x || !y || !out || n < 0 || !(tau > 0.0)) return PCS_EINVAL;
+  if (n == 0) return PCS_OK;
+  PCS_DISPATCH(dt, k_prox_kl<T><<<grid_for(n, 256), 256, 0, st>>>((const T*)x, (const T*)y, (T*)out, n, tau));
+  return launch_status();
+}
+
+int pcs_prox_logbarrier(int dt, const void* x, void* out, int64_t n, double tau, hipStream_t st) {
+  if ((dt != PCS_F32 && dt != PCS_F64) || !x || !out || n < 0 || !(tau > 0.0)) return PCS_EINVAL;
+  if (n == 0) return PCS_OK;
+  PCS_DISPATCH(dt, k_prox_logbarrier<T><<<grid_for(n, 256), 256, 0, st>>>((const T*)x, (T*)out, n, tau));
+  return launch_status();
+}
+
+int pcs_prox_entropy(int dt, const void* x, void* out, int64_t n, double tau, hipStream_t st) {
+  if ((dt != PCS_F32 && dt != PCS_F64) || !x || !out || n < 0 || !(tau > 0.0)) return PCS_EINVAL;
+  if (n == 0) return PCS_OK;
+  PCS_DISPATCH(dt, k_prox_entropy<T><<<grid_for(n, 256), 256, 0, st>>>((const T*)x, (T*)out, n, tau, log(tau)));
   return launch_status();
 }
 

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .. import _ops as O
-from ..core.functional import DifferentiableFunctional
+from ..core.functional import DifferentiableFunctional, ProximableFunctional
 from .base import IndicatorFunctional, LpNorm
 
 
@@ -211,3 +211,91 @@ def LInftyBall(dim, radius):
     """``penalty.py:420-477``: indicator of the L-infinity ball (clip)."""
     return IndicatorFunctional(dim=dim, condition_func=lambda t: float(t.abs().max()) <= radius,
                                projection_func=lambda t: O.proj_segment(t, -radius, radius))
+
+
+class SquaredL1Norm(ProximableFunctional):
+    """``(sum |x_i|)^2`` (``penalty.py:248-316``).  Both ``prox_computation`` values ('sort', [OnKerLearn]
+    Algorithm 2, and 'root', [FirstOrd] Lemma 6.70 -- the same minimiser) run the threshold kernel with
+    ``a = 0, b = 1 / (2 tau)``: ``t = 2 tau / (1 + 2 tau k) S_k``, then a soft threshold.  A zero input
+    returns zeros (the reference's 'sort' branch raises on it)."""
+
+    def __init__(self, dim, prox_computation='sort'):
+        if prox_computation not in ('sort', 'root'):
+            raise ValueError(f"prox_computation must be 'sort' or 'root', got {prox_computation!r}")
+        self.prox_computation = prox_computation
+        super().__init__(dim=dim, data=None, is_differentiable=False, is_linear=False)
+
+    def _apply(self, t):
+        return float(O.reduce_dev(1, t).item()) ** 2
+
+    def _prox(self, t, tau):
+        return O.thresh_l1(t, 0.0, 1.0 / (2.0 * tau), 'soft')
+
+
+def L1Ball(dim, radius):
+    """``penalty.py:319-377``: indicator of the L1 ball; the projection (``math/prox.py:158-164``) is the
+    threshold kernel with ``a = radius, b = 0``, decided and applied on the device."""
+    return IndicatorFunctional(dim=dim, condition_func=lambda t: float(O.reduce_dev(1, t).item()) <= radius,
+                               projection_func=lambda t: O.thresh_l1(t, radius, 0.0, 'soft'))
+
+
+class LInftyNorm(LpNorm):
+    """``max |x_i|`` (``penalty.py:380-417``): ``prox = x - tau * proj_l1_ball(x / tau, 1)``, which is a
+    clip of x at the threshold t with ``sum max(|x| - t, 0) = tau``."""
+
+    def __init__(self, dim):
+        from ..math.prox import proj_l1_ball
+        super().__init__(dim=dim, proj_lq_ball=proj_l1_ball)
+
+    def _apply(self, t):
+        return float(t.abs().max())
+
+    def _prox(self, t, tau):
+        return O.thresh_l1(t, tau, 0.0, 'clip')
+
+
+class LogBarrier(ProximableFunctional):
+    """``-sum log x_i`` (``penalty.py:770-840``)."""
+
+    def __init__(self, dim):
+        super().__init__(dim=dim, data=None, is_differentiable=False, is_linear=False)
+
+    def _apply(self, t):
+        if bool(torch.any(t <= 0)):
+            return np.inf
+        return -float(torch.log(t.double()).sum())
+
+    def _prox(self, t, tau):
+        return O.prox_logbarrier(t, tau)
+
+
+class ShannonEntropy(ProximableFunctional):
+    """``sum x_i log x_i`` (``penalty.py:843-922``; 0 at 0, +inf for negative entries)."""
+
+    def __init__(self, dim):
+        super().__init__(dim=dim, data=None, is_differentiable=False, is_linear=False)
+
+    def _apply(self, t):
+        if bool(torch.any(t < 0)):
+            return np.inf
+        return float(torch.special.xlogy(t.double(), t.double()).sum())
+
+    def _prox(self, t, tau):
+        return O.prox_entropy(t, tau)
+
+
+class QuadraticForm(DifferentiableFunctional):
+    """``<x, L x>`` for a positive-definite ``linop`` (identity if None), ``penalty.py:925-990``."""
+
+    def __init__(self, dim, linop=None):
+        self.linop = linop
+        diff_lipschitz_cst = 2 if linop is None else 2 * linop.diff_lipschitz_cst  # penalty.py:973-978
+        super().__init__(dim=dim, data=None, is_linear=False, diff_lipschitz_cst=diff_lipschitz_cst)
+
+    def _apply(self, t):
+        if self.linop is None:
+            return float(O.reduce_dev(0, t).item())
+        return float(O.reduce_dev(3, t, self.linop._apply(t)).item())
+
+    def _jacT(self, t):
+        return O.scale(t if self.linop is None else self.linop._apply(t), 2.0)

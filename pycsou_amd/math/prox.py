@@ -24,6 +24,14 @@ def soft(x, tau):
     return O.like(out, x)
 
 
+def proj_l1_ball(x, radius):
+    """``prox.py:117-164``: ``x`` if ``sum|x| <= radius``, else ``soft(x, mu)`` with
+    ``sum max(|x| - mu, 0) = radius``; mu is located exactly on the device (``pcs_thresh_l1``) where the
+    reference runs ``brentq`` on the host."""
+    t = O.to_dev(x)
+    return O.like(O.thresh_l1(t, radius, 0.0, 'soft'), x)
+
+
 def proj_l2_ball(x, radius):
     """``prox.py:167-210``."""
     t = O.to_dev(x)
