@@ -76,6 +76,43 @@ int pcs_lap_fwd(int dtype, const void* x, void* out, const int64_t* dims, const 
 int pcs_lap_adj(int dtype, const void* y, void* out, const int64_t* dims, const double* weights,
                 const double* steps, int edge, hipStream_t stream);
 
+/* FirstDirectionalDerivative (pycsou/linop/diff.py:380-486 -> pylops 1.x Sum(axis 0) * Diagonal(v) *
+ * Gradient), one launch: out[p] = scale * ((v_0[p] (D_0 x)[p] + v_1[p] (D_1 x)[p]) + v_2[p] (D_2 x)[p]),
+ * ndim in 1..3, steps[ndim].  `v` is a device buffer of dtype: ndim scalars (v_is_field == 0) or ndim * N
+ * values in [k][p] order.  `kill` is 0 or 2: outputs within `kill` samples of either end of any axis are
+ * written as 0 (the kill-edge mask of SecondDirectionalDerivative, diff.py:598-605; an axis shorter than
+ * 2 * kill zeroes everything).  The adjoint is out = scale * sum_k D_k^T (v_k . y), accumulated in axis
+ * order as pcs_grad_adj, with the same `kill` on its output.  With them SecondDirectionalDerivative
+ * = mask . (-Dv^T Dv) is pcs_dirderiv_fwd followed by pcs_dirderiv_adj(scale = -1, kill = 2).
+ * x == out is rejected; a negative dim is PCS_EINVAL, a zero dim an empty array (0, no launch).
+ * Arguments are checked before any device call; nothing allocates or synchronises. */
+int pcs_dirderiv_fwd(int dtype, const void* x, const void* v, int v_is_field, void* out, int ndim,
+                     const int64_t* dims, const double* steps, int kind, int edge, double scale, int kill,
+                     hipStream_t stream);
+int pcs_dirderiv_adj(int dtype, const void* y, const void* v, int v_is_field, void* out, int ndim,
+                     const int64_t* dims, const double* steps, int kind, int edge, double scale, int kill,
+                     hipStream_t stream);
+
+/* Integration1D (pycsou/linop/diff.py:1071-1137 -> pylops 1.x CausalIntegration, halfcurrent=False):
+ * out[i] = step * sum_{j <= i} x[j] along `axis` of a C-order array (ndim in 1..32), or with
+ * reverse != 0 the adjoint step * sum_{j >= i} x[j] (indexed backwards, no flipped copy).  Sums are
+ * carried in fp64 for both dtypes and multiplied by `step` last.  The axis is seen as the middle of
+ * (outer, n, inner): inner > 1 marches threads along n with coalesced loads across inner; inner == 1
+ * scans each line with wave-level shuffles and a carried prefix.  When there are too few lines to fill
+ * the device a line is cut into segments of at least PCS_CUMSUM_SPAN (inner == 1) or
+ * PCS_CUMSUM_SPAN_STRIDED (inner > 1) samples and handled reduce-then-scan in three launches (segment
+ * totals into ws, a scan of the totals, the offset scan); no workgroup ever waits for another.  ws then
+ * holds pcs_cumsum_ws_bytes(ndim, dims, axis) bytes, 8-byte aligned (the function returns 0 when no
+ * workspace is needed, -1 on bad arguments, and never decreases in the axis length; it stays below
+ * PCS_CUMSUM_WS_MAX for any shape).  x == out is allowed: every sample is read and written by the same
+ * thread.  A negative dim is PCS_EINVAL, a zero dim an empty array (0, no launch). */
+#define PCS_CUMSUM_SPAN 2048
+#define PCS_CUMSUM_SPAN_STRIDED 64
+#define PCS_CUMSUM_WS_MAX (2 * 1024 * 1024 + 64 * 1024)
+int64_t pcs_cumsum_ws_bytes(int ndim, const int64_t* dims, int axis);
+int pcs_cumsum(int dtype, const void* x, void* out, int ndim, const int64_t* dims, int axis, double step,
+               int reverse, void* ws, hipStream_t stream);
+
 /* Convolve2D (pycsou/linop/conv.py:167-295 -> pylops Convolve2D, 'same', zero boundary):
  * out[i] = sum_j h[j] x[i + off - j] (+ beta * b[i] if b != NULL).  `psf` is a device
  * buffer kh*kw of dtype.  The adjoint (correlation) is this call with the flipped PSF

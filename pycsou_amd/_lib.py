@@ -22,6 +22,9 @@ PCS_G_NULL, PCS_G_NONNEG, PCS_G_SEGMENT = 0, 1, 2
 PCS_APGD_G_L1 = 3
 PCS_THRESH_SOFT, PCS_THRESH_CLIP = 0, 1
 PCS_THRESH_PIVOTS = 31
+# pcs_cumsum: shortest segment of a split line (contiguous / strided layout) and the workspace bound
+PCS_CUMSUM_SPAN, PCS_CUMSUM_SPAN_STRIDED = 2048, 64
+PCS_CUMSUM_WS_MAX = 2 * 1024 * 1024 + 64 * 1024
 PCS_F_NULL, PCS_F_DENOISE, PCS_F_SEPCONV, PCS_F_GRADBUF, PCS_F_CONV2D, PCS_F_CONV0 = 0, 1, 2, 3, 4, 5
 PCS_M_NONE, PCS_M_L1LOSS = 0, 1
 # pcs_pds2d_path: the kernel family of a fused 2-D step
@@ -118,6 +121,12 @@ _SIGS = {
     'pcs_grad_adj': (_c_int, [_c_int, _vp, _vp, _c_int, _pi64, _pdbl, _c_int, _c_int, _vp]),
     'pcs_lap_fwd': (_c_int, [_c_int, _vp, _vp, _pi64, _pdbl, _pdbl, _c_int, _vp]),
     'pcs_lap_adj': (_c_int, [_c_int, _vp, _vp, _pi64, _pdbl, _pdbl, _c_int, _vp]),
+    'pcs_dirderiv_fwd': (_c_int, [_c_int, _vp, _vp, _c_int, _vp, _c_int, _pi64, _pdbl, _c_int, _c_int, _c_dbl, _c_int,
+                                  _vp]),
+    'pcs_dirderiv_adj': (_c_int, [_c_int, _vp, _vp, _c_int, _vp, _c_int, _pi64, _pdbl, _c_int, _c_int, _c_dbl, _c_int,
+                                  _vp]),
+    'pcs_cumsum_ws_bytes': (_c_i64, [_c_int, _pi64, _c_int]),
+    'pcs_cumsum': (_c_int, [_c_int, _vp, _vp, _c_int, _pi64, _c_int, _c_dbl, _c_int, _vp, _vp]),
     'pcs_conv2d': (_c_int, [_c_int, _vp, _vp, _c_i64, _c_i64, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_dbl,
                             _vp]),
     'pcs_conv2d_plan_tier': (_c_int, [_c_int, _c_int, _c_int, _c_int]),

@@ -325,6 +325,59 @@ def deriv2(x, dims, axis, step, edge, adjoint=False):
     return out
 
 
+def _dense_on(device, *tensors):
+    """The kernels take raw pointers: every tensor contiguous and on `device`, a GPU."""
+    return device.type == 'cuda' and all(t.is_contiguous() and t.device == device for t in tensors)
+
+
+def dirderiv(x, v, v_is_field, dims, steps, kind, edge, adjoint=False, scale=1.0, kill=0):
+    """Fused directional derivative ``scale * sum_k v_k . D_k x`` or its adjoint ``scale * sum_k D_k^T (v_k . y)``
+    (``pcs_dirderiv_*``, 1-D to 3-D); ``v``: device tensor of ``ndim`` scalars or ``ndim * N`` values in [k][p]
+    order; ``kill`` (0 or 2) zeroes that many samples at both ends of every axis of the output."""
+    lib = L.gpu()
+    if v.dtype != x.dtype or v.numel() != (len(dims) * x.numel() if v_is_field else len(dims)):
+        raise ValueError('dirderiv: directions must have the dtype of x and ndim or ndim * N values')
+    if int(np.prod(dims)) != x.numel() or not _dense_on(x.device, x, v):
+        raise ValueError('dirderiv: x and directions must be contiguous tensors on one GPU, x of prod(dims) elements')
+    out = torch.empty_like(x)
+    fn = lib.pcs_dirderiv_adj if adjoint else lib.pcs_dirderiv_fwd
+    L.check(fn(L.dtcode(x), L.ptr(x), L.ptr(v), int(bool(v_is_field)), L.ptr(out), len(dims), L.i64s(dims),
+               L.dbls(steps), L.KINDS[kind], int(bool(edge)), float(scale), int(kill), L.stream()), 'pcs_dirderiv')
+    return out
+
+
+# shortest segment of a line that pcs_cumsum splits (contiguous axis / strided axis): lines of SPAN + 1 and
+# 2 SPAN + 1 samples are the first with two and three segments
+CUMSUM_SPAN, CUMSUM_SPAN_STRIDED = L.PCS_CUMSUM_SPAN, L.PCS_CUMSUM_SPAN_STRIDED
+
+
+def _cumsum_ws(t):
+    """Workspace of pcs_cumsum (bounded for any shape by PCS_CUMSUM_WS_MAX), cached per device like
+    ``_thresh_ws`` so that a captured loop replays with the buffer it was captured with."""
+    key = (t.device, 'cumsum')
+    ws = _ws_cache.get(key)
+    if ws is None:
+        ws = torch.empty(L.PCS_CUMSUM_WS_MAX // 8, dtype=torch.float64, device=t.device)
+        _ws_cache[key] = ws
+    return ws
+
+
+def cumsum(x, dims, axis, step, reverse=False, out=None):
+    """``step * cumsum(x, axis)`` of a C-order array of shape ``dims`` (``pcs_cumsum``), or with ``reverse`` the
+    sum from the far end of the axis (the adjoint).  ``out`` may be ``x`` itself."""
+    lib = L.gpu()
+    out = torch.empty_like(x) if out is None else out
+    d = L.i64s(dims)
+    ws = _cumsum_ws(x)
+    need = int(lib.pcs_cumsum_ws_bytes(len(dims), d, int(axis)))
+    if need < 0 or need > ws.numel() * 8 or int(np.prod(dims)) != x.numel() or out.numel() != x.numel() \
+            or out.dtype != x.dtype or not _dense_on(x.device, x, out):
+        raise ValueError('cumsum: shape, axis and tensors do not agree (x and out: contiguous, same dtype, one GPU)')
+    L.check(lib.pcs_cumsum(L.dtcode(x), L.ptr(x), L.ptr(out), len(dims), d, int(axis), float(step),
+                           int(bool(reverse)), L.ptr(ws), L.stream()), 'pcs_cumsum')
+    return out
+
+
 def gather(x, idx):
     """x[idx] (idx: int32 device tensor)."""
     lib = L.gpu()

@@ -101,6 +101,66 @@ __global__ void k_grad_adj(const T* __restrict__ z, T* __restrict__ out, Geo3 g,
   }
 }
 
+// ---- directional derivatives (pycsou/linop/diff.py:380-606; PyLops 1.x FirstDirectionalDerivative =
+// Sum(axis 0) * Diagonal(v) * Gradient): one launch each way.  v holds nd scalars (FIELD = false) or nd * N
+// values in [k][p] order.  `kill` (0 or 2) zeroes the outputs within that many samples of either end of any
+// axis -- the reference's kill-edge mask of SecondDirectionalDerivative -- and `scale` multiplies the rest.
+__device__ __forceinline__ bool killed(const Geo3& g, int64_t p, int nd, int kill) {
+  if (kill == 0) return false;
+  for (int a = 3 - nd; a < 3; ++a) {
+    const int64_t i = coord(g, p, a);
+    if (i < kill || i >= g.n[a] - kill) return true;
+  }
+  return false;
+}
+
+// y[p] = (v_0[p] (D_0 x)[p] + v_1[p] (D_1 x)[p]) + v_2[p] (D_2 x)[p], summed in axis order
+template <typename T, bool FIELD>
+__global__ void k_dirderiv_fwd(const T* __restrict__ x, const T* __restrict__ v, T* __restrict__ out, Geo3 g, int nd,
+                               T h0, T h1, T h2, int kind, int edge, T scale, int kill) {
+  const T hs[3] = {h0, h1, h2};
+  for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < g.N; p += (int64_t)gridDim.x * blockDim.x) {
+    if (killed(g, p, nd, kill)) {
+      out[p] = T(0);
+      continue;
+    }
+    T acc = T(0);
+    for (int k = 0; k < nd; ++k) {
+      const T t = (FIELD ? v[k * g.N + p] : v[k]) * d1_fwd_at(x, g, p, 3 - nd + k, hs[k], kind, edge);
+      acc = (k == 0) ? t : acc + t;
+    }
+    out[p] = scale * acc;
+  }
+}
+
+// the adjoint's sample at a neighbour index q: v_k[q] * y[q]
+template <typename T, bool FIELD>
+struct DirLoad {
+  const T* __restrict__ y;
+  const T* __restrict__ v;  // block k of the field, or the scalar v_k
+  __device__ __forceinline__ T operator()(int64_t q) const { return (FIELD ? v[q] : v[0]) * y[q]; }
+};
+
+// out[p] = sum_k (D_k^T (v_k . y))[p], accumulated in axis order as k_grad_adj does
+template <typename T, bool FIELD>
+__global__ void k_dirderiv_adj(const T* __restrict__ y, const T* __restrict__ v, T* __restrict__ out, Geo3 g, int nd,
+                               T h0, T h1, T h2, int kind, int edge, T scale, int kill) {
+  const T hs[3] = {h0, h1, h2};
+  for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < g.N; p += (int64_t)gridDim.x * blockDim.x) {
+    if (killed(g, p, nd, kill)) {
+      out[p] = T(0);
+      continue;
+    }
+    T acc = T(0);
+    for (int k = 0; k < nd; ++k) {
+      const int a = 3 - nd + k;
+      const DirLoad<T, FIELD> ld{y, FIELD ? v + k * g.N : v + k};
+      acc += d1_adj_core_ld<T, int64_t>(ld, p, g.s[a], coord(g, p, a), g.n[a], hs[k], kind, edge);
+    }
+    out[p] = scale * acc;
+  }
+}
+
 // SecondDerivative (pylops 1.x) along axis a at p, and its adjoint
 template <typename T>
 __device__ __forceinline__ T d2_fwd_at(const T* __restrict__ x, const Geo3& g, int64_t p, int a, T h2, int edge) {
@@ -200,6 +260,42 @@ static int lap(bool adj, const void* in, void* out, const int64_t* dims, const d
   return launch_status();
 }
 
+template <typename T>
+static int dirderiv(bool adj, const void* in, const void* v, int v_is_field, void* out, int ndim, const int64_t* dims,
+                    const double* steps, int kind, int edge, double scale, int kill, hipStream_t st) {
+  if (ndim < 1 || ndim > 3 || !dims || !steps || !in || !v || !out || in == out || kind < 0 || kind > 2 ||
+      (kill != 0 && kill != 2))
+    return PCS_EINVAL;
+  int64_t d[3];
+  bool empty = false;
+  for (int k = 0; k < ndim; ++k) {
+    if (dims[k] < 0) return PCS_EINVAL;
+    empty |= dims[k] == 0;
+    d[k] = dims[k];
+  }
+  if (empty) return PCS_OK;
+  Geo3 g;
+  if (!make_geo(ndim, d, g)) return PCS_EINVAL;
+  const T h0 = (T)steps[0], h1 = ndim > 1 ? (T)steps[1] : T(1), h2 = ndim > 2 ? (T)steps[2] : T(1);
+  const unsigned grid = grid_for(g.N, 256);
+  const T* a = (const T*)in;
+  const T* vv = (const T*)v;
+  T* o = (T*)out;
+  const int e = edge ? 1 : 0;
+  if (!adj) {
+    if (v_is_field)
+      k_dirderiv_fwd<T, true><<<grid, 256, 0, st>>>(a, vv, o, g, ndim, h0, h1, h2, kind, e, (T)scale, kill);
+    else
+      k_dirderiv_fwd<T, false><<<grid, 256, 0, st>>>(a, vv, o, g, ndim, h0, h1, h2, kind, e, (T)scale, kill);
+  } else {
+    if (v_is_field)
+      k_dirderiv_adj<T, true><<<grid, 256, 0, st>>>(a, vv, o, g, ndim, h0, h1, h2, kind, e, (T)scale, kill);
+    else
+      k_dirderiv_adj<T, false><<<grid, 256, 0, st>>>(a, vv, o, g, ndim, h0, h1, h2, kind, e, (T)scale, kill);
+  }
+  return launch_status();
+}
+
 }  // namespace pcs
 
 using namespace pcs;
@@ -261,6 +357,20 @@ int pcs_lap_adj(int dt, const void* y, void* out, const int64_t* dims, const dou
                 hipStream_t st) {
   if (dt == PCS_F32) return lap<float>(true, y, out, dims, w, steps, edge, st);
   if (dt == PCS_F64) return lap<double>(true, y, out, dims, w, steps, edge, st);
+  return PCS_EINVAL;
+}
+
+int pcs_dirderiv_fwd(int dt, const void* x, const void* v, int v_is_field, void* out, int ndim, const int64_t* dims,
+                     const double* steps, int kind, int edge, double scale, int kill, hipStream_t st) {
+  if (dt == PCS_F32) return dirderiv<float>(false, x, v, v_is_field, out, ndim, dims, steps, kind, edge, scale, kill, st);
+  if (dt == PCS_F64) return dirderiv<double>(false, x, v, v_is_field, out, ndim, dims, steps, kind, edge, scale, kill, st);
+  return PCS_EINVAL;
+}
+
+int pcs_dirderiv_adj(int dt, const void* y, const void* v, int v_is_field, void* out, int ndim, const int64_t* dims,
+                     const double* steps, int kind, int edge, double scale, int kill, hipStream_t st) {
+  if (dt == PCS_F32) return dirderiv<float>(true, y, v, v_is_field, out, ndim, dims, steps, kind, edge, scale, kill, st);
+  if (dt == PCS_F64) return dirderiv<double>(true, y, v, v_is_field, out, ndim, dims, steps, kind, edge, scale, kill, st);
   return PCS_EINVAL;
 }
 

@@ -10,40 +10,58 @@
 
 namespace pcs {
 
+// The first-derivative cores take their samples through a load functor ld(q) -> T, so one copy of the
+// edge rules serves a plain array (PtrLoad) and a product formed at the neighbour index (the directional
+// adjoint's v_k[q] * y[q], stencil.hip)
+template <typename T>
+struct PtrLoad {
+  const T* __restrict__ a;
+  template <typename I>
+  __device__ __forceinline__ T operator()(I q) const { return a[q]; }
+};
+
 // D x at p (FirstDerivative._matvec_{forward,backward,centered})
+template <typename T, typename I, typename L>
+__device__ __forceinline__ T d1_fwd_core_ld(L x, I p, I s, I i, I n, T h, int kind, int edge) {
+  if (kind == PCS_FORWARD) {
+    return (i < n - 1) ? (x(p + s) - x(p)) / h : T(0);
+  } else if (kind == PCS_BACKWARD) {
+    return (i > 0) ? (x(p) - x(p - s)) / h : T(0);
+  }
+  if (i > 0 && i < n - 1) return (T(0.5) * x(p + s) - T(0.5) * x(p - s)) / h;
+  if (!edge || n < 2) return T(0);
+  return (i == 0) ? (x(p + s) - x(p)) / h : (x(p) - x(p - s)) / h;
+}
 template <typename T, typename I>
 __device__ __forceinline__ T d1_fwd_core(const T* __restrict__ x, I p, I s, I i, I n, T h, int kind, int edge) {
-  if (kind == PCS_FORWARD) {
-    return (i < n - 1) ? (x[p + s] - x[p]) / h : T(0);
-  } else if (kind == PCS_BACKWARD) {
-    return (i > 0) ? (x[p] - x[p - s]) / h : T(0);
-  }
-  if (i > 0 && i < n - 1) return (T(0.5) * x[p + s] - T(0.5) * x[p - s]) / h;
-  if (!edge || n < 2) return T(0);
-  return (i == 0) ? (x[p + s] - x[p]) / h : (x[p] - x[p - s]) / h;
+  return d1_fwd_core_ld<T, I, PtrLoad<T>>(PtrLoad<T>{x}, p, s, i, n, h, kind, edge);
 }
 
 // (D^T y) at p (FirstDerivative._rmatvec_*), accumulation order of the slicing code
-template <typename T, typename I>
-__device__ __forceinline__ T d1_adj_core(const T* __restrict__ y, I p, I s, I i, I n, T h, int kind, int edge) {
+template <typename T, typename I, typename L>
+__device__ __forceinline__ T d1_adj_core_ld(L y, I p, I s, I i, I n, T h, int kind, int edge) {
   T acc = T(0);
   if (kind == PCS_FORWARD) {
-    if (i < n - 1) acc -= y[p] / h;
-    if (i > 0) acc += y[p - s] / h;
+    if (i < n - 1) acc -= y(p) / h;
+    if (i > 0) acc += y(p - s) / h;
   } else if (kind == PCS_BACKWARD) {
-    if (i < n - 1) acc -= y[p + s] / h;
-    if (i > 0) acc += y[p] / h;
+    if (i < n - 1) acc -= y(p + s) / h;
+    if (i > 0) acc += y(p) / h;
   } else {
-    if (i <= n - 3) acc -= (T(0.5) * y[p + s]) / h;
-    if (i >= 2) acc += (T(0.5) * y[p - s]) / h;
+    if (i <= n - 3) acc -= (T(0.5) * y(p + s)) / h;
+    if (i >= 2) acc += (T(0.5) * y(p - s)) / h;
     if (edge && n >= 2) {
-      if (i == 0) acc -= y[p] / h;
-      if (i == 1) acc += y[p - s] / h;
-      if (i == n - 2) acc -= y[p + s] / h;
-      if (i == n - 1) acc += y[p] / h;
+      if (i == 0) acc -= y(p) / h;
+      if (i == 1) acc += y(p - s) / h;
+      if (i == n - 2) acc -= y(p + s) / h;
+      if (i == n - 1) acc += y(p) / h;
     }
   }
   return acc;
+}
+template <typename T, typename I>
+__device__ __forceinline__ T d1_adj_core(const T* __restrict__ y, I p, I s, I i, I n, T h, int kind, int edge) {
+  return d1_adj_core_ld<T, I, PtrLoad<T>>(PtrLoad<T>{y}, p, s, i, n, h, kind, edge);
 }
 
 // SecondDerivative x at p (h2 = sampling^2)

@@ -162,3 +162,11 @@ def deriv2_norm2(n, edge, h):
 
 def conv1d_norm2(n, taps, off):
     return _lam_max_gram(conv1d_matrix(int(n), taps, int(off)))
+
+
+def integration_norm(n, step=1.0):
+    """||step * L|| of the n x n causal-integration matrix L (ones on and below the diagonal;
+    ``Integration1D``, ``pycsou/linop/diff.py:1071-1137``), in closed form: L^{-1} is the backward
+    difference, so (L L^T)^{-1} is the tridiagonal second-difference matrix with one Neumann end, whose
+    smallest eigenvalue is 4 sin^2(pi / (4n + 2)); hence ||L|| = 1 / (2 sin(pi / (4n + 2)))."""
+    return abs(float(step)) / (2.0 * np.sin(np.pi / (4 * int(n) + 2)))
