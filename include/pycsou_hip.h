@@ -198,6 +198,45 @@ int pcs_conv0_residual_adjoint(int dtype, const void* t, const void* y, void* s,
 int pcs_gather(int dtype, const void* x, const int32_t* idx, void* out, int64_t m, hipStream_t stream);
 int pcs_gather_or_zero(int dtype, const void* y, const int32_t* inv, void* out, int64_t n, hipStream_t stream);
 
+/* CSR sparse matrix-vector product out = A x (SparseLinearOperator, pycsou/linop/base.py:121-137 ->
+ * csr_matrix.dot; the sparse MappedDistanceMatrix, sampling.py:975-1007; the adjoint of NNSampling,
+ * sampling.py:680-687).  A is nrows x ncols with nnz entries: rowptr[nrows + 1] int64, colind[nnz] int32
+ * (ncols < 2^31), vals[nnz] and x[ncols] of `dtype`; out[nrows] must not overlap x.  A transposed product is
+ * this entry point on the CSR of A^T, which the caller builds once.
+ *  - `lanes` (a power of two in 1..64, chosen once per matrix from nnz / nrows) lanes serve one row of at
+ *    most PCS_SPMV_LONG_ROW entries: lane j adds entries j, j + lanes, ... in order, then a fixed xor tree.
+ *  - Every longer row is cut by the caller into chunks of PCS_SPMV_CHUNK entries (the last one shorter), listed
+ *    row by row: chunk c covers entries chunk_start[c] .. of row chunk_row[c]; long row i is long_row[i] and
+ *    owns chunks long_first[i] .. long_first[i + 1] - 1 (long_first has nlong + 1 entries, all four lists are
+ *    int64 device arrays).  One workgroup sums one chunk into partials[c] (nchunks doubles, 8-byte aligned),
+ *    then one thread per long row adds its partials in chunk order.  A row of more than PCS_SPMV_LONG_ROW
+ *    entries that is not listed is left unwritten.
+ * Sums are carried in fp64 and rounded once.  The order of every sum depends on (rowptr, lanes) alone, so two
+ * calls return the same bits; there are no atomics.  Empty matrices and empty rows are legal (an empty row
+ * gives 0); colind, vals and x may be null when nnz == 0.  PCS_EINVAL before any device call for a null
+ * pointer, a negative size, ncols >= 2^31, lanes not a power of two in 1..64, an unknown dtype, chunk lists
+ * that cannot belong to nnz entries, or out overlapping x.  The device arrays are trusted: the caller
+ * validates rowptr, colind and the chunk lists on the host when it builds them. */
+#define PCS_SPMV_LONG_ROW 4096
+#define PCS_SPMV_CHUNK 4096
+int pcs_csr_spmv(int dtype, int64_t nrows, int64_t ncols, int64_t nnz, const int64_t* rowptr, const int32_t* colind,
+                 const void* vals, const void* x, void* out, int lanes, int64_t nchunks, const int64_t* chunk_row,
+                 const int64_t* chunk_start, int64_t nlong, const int64_t* long_row, const int64_t* long_first,
+                 void* partials, hipStream_t stream);
+
+/* Block pooling of a C-order array of ndim in 1..3 axes (Pooling, pycsou/linop/sampling.py:394-536 ->
+ * skimage.measure.block_reduce with cval = 0) and its unpooling (Pooling.adjoint, np.repeat and crop).
+ * dims[ndim] is the shape of the UNPOOLED array in both calls, block[ndim] >= 1 the block sizes; the pooled
+ * array has ceil(dims[k] / block[k]) entries per axis.
+ *   pcs_pool_fwd:  out[b] = scale * (sum of x over the real cells of block b)   -- a ragged block is zero padded
+ *   pcs_pool_adj:  out[p] = scale * y[block of p]
+ * Fixed summation order in fp64, no atomics; a block may be wider than a workgroup or larger than its axis.
+ * x == out is rejected; a negative dim or a block < 1 is PCS_EINVAL, a zero dim an empty array (0, no launch). */
+int pcs_pool_fwd(int dtype, const void* x, void* out, int ndim, const int64_t* dims, const int64_t* block,
+                 double scale, hipStream_t stream);
+int pcs_pool_adj(int dtype, const void* y, void* out, int ndim, const int64_t* dims, const int64_t* block,
+                 double scale, hipStream_t stream);
+
 /* ---------------------------------------------------------------- prox / functionals */
 
 /* L1Norm.prox (pycsou/func/penalty.py:194-245 via LpNorm.prox, func/base.py:239-240):

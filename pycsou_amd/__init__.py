@@ -11,8 +11,8 @@ import sys
 __version__ = '0.1.0'
 
 _SUBMODULES = ('core', 'core.map', 'core.linop', 'core.functional', 'core.solver', 'linop', 'linop.base',
-               'linop.conv', 'linop.diff', 'func', 'func.base', 'func.penalty', 'func.loss', 'math', 'math.prox',
-               'opt', 'opt.proxalgs', 'util', 'util.misc')
+               'linop.conv', 'linop.diff', 'linop.sampling', 'func', 'func.base', 'func.penalty', 'func.loss', 'math',
+               'math.prox', 'opt', 'opt.proxalgs', 'util', 'util.misc')
 
 
 def install_alias(name='pycsou'):

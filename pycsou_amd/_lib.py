@@ -25,6 +25,8 @@ PCS_THRESH_PIVOTS = 31
 # pcs_cumsum: shortest segment of a split line (contiguous / strided layout) and the workspace bound
 PCS_CUMSUM_SPAN, PCS_CUMSUM_SPAN_STRIDED = 2048, 64
 PCS_CUMSUM_WS_MAX = 2 * 1024 * 1024 + 64 * 1024
+# pcs_csr_spmv: rows of more than LONG_ROW entries are cut into chunks of CHUNK entries
+PCS_SPMV_LONG_ROW, PCS_SPMV_CHUNK = 4096, 4096
 PCS_F_NULL, PCS_F_DENOISE, PCS_F_SEPCONV, PCS_F_GRADBUF, PCS_F_CONV2D, PCS_F_CONV0 = 0, 1, 2, 3, 4, 5
 PCS_M_NONE, PCS_M_L1LOSS = 0, 1
 # pcs_pds2d_path: the kernel family of a fused 2-D step
@@ -117,6 +119,10 @@ _SIGS = {
     'pcs_deriv2_adj': (_c_int, [_c_int, _vp, _vp, _c_int, _pi64, _c_int, _c_dbl, _c_int, _vp]),
     'pcs_gather': (_c_int, [_c_int, _vp, _vp, _vp, _c_i64, _vp]),
     'pcs_gather_or_zero': (_c_int, [_c_int, _vp, _vp, _vp, _c_i64, _vp]),
+    'pcs_csr_spmv': (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_int, _c_i64, _vp, _vp, _c_i64,
+                              _vp, _vp, _vp, _vp]),
+    'pcs_pool_fwd': (_c_int, [_c_int, _vp, _vp, _c_int, _pi64, _pi64, _c_dbl, _vp]),
+    'pcs_pool_adj': (_c_int, [_c_int, _vp, _vp, _c_int, _pi64, _pi64, _c_dbl, _vp]),
     'pcs_grad_fwd': (_c_int, [_c_int, _vp, _vp, _c_int, _pi64, _pdbl, _c_int, _c_int, _vp]),
     'pcs_grad_adj': (_c_int, [_c_int, _vp, _vp, _c_int, _pi64, _pdbl, _c_int, _c_int, _vp]),
     'pcs_lap_fwd': (_c_int, [_c_int, _vp, _vp, _pi64, _pdbl, _pdbl, _c_int, _vp]),

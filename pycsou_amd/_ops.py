@@ -395,6 +395,112 @@ def gather_or_zero(y, inv):
     return out
 
 
+# pcs_csr_spmv: a row of more than SPMV_LONG_ROW entries is cut into chunks of SPMV_CHUNK entries (rows of
+# LONG_ROW + 1 and 2 CHUNK + 1 entries are the first with two and three chunks)
+SPMV_LONG_ROW, SPMV_CHUNK = L.PCS_SPMV_LONG_ROW, L.PCS_SPMV_CHUNK
+
+
+def spmv_lanes(nnz, nrows):
+    """Lanes per row of pcs_csr_spmv: the smallest power of two >= nnz / nrows, at most a wave."""
+    mean = nnz / max(int(nrows), 1)
+    lanes = 1
+    while lanes < 64 and lanes < mean:
+        lanes *= 2
+    return lanes
+
+
+def spmv_plan(rowptr):
+    """Chunk lists of pcs_csr_spmv for a CSR row-pointer array: (chunk_row, chunk_start, long_row, long_first),
+    int64 NumPy arrays.  Rows of more than SPMV_LONG_ROW entries, in row order, each cut into chunks of SPMV_CHUNK
+    entries in entry order."""
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    length = np.diff(rowptr)
+    long_row = np.flatnonzero(length > SPMV_LONG_ROW).astype(np.int64)
+    per_row = -(-length[long_row] // SPMV_CHUNK)
+    long_first = np.concatenate([[0], np.cumsum(per_row)]).astype(np.int64)
+    chunk_row = np.repeat(long_row, per_row)
+    within = np.arange(int(long_first[-1]), dtype=np.int64) - np.repeat(long_first[:-1], per_row)
+    chunk_start = rowptr[chunk_row] + within * SPMV_CHUNK
+    return chunk_row, chunk_start.astype(np.int64), long_row, long_first
+
+
+class DeviceCSR:
+    """A fixed SciPy sparse matrix as the device arrays of pcs_csr_spmv in one dtype: int64 row pointers, int32
+    column indices, values, the chunk lists of its long rows and their partials workspace.  Everything is
+    validated and built once on the host, so a captured loop replays with the buffers it was captured with."""
+
+    def __init__(self, mat, dtype):
+        import scipy.sparse as sp
+        L.gpu()
+        m = sp.csr_matrix(mat)
+        nrows, ncols = m.shape
+        if ncols >= 2 ** 31:
+            raise NotImplementedError('pcs_csr_spmv indexes columns with int32 (ncols < 2^31)')
+        rowptr, colind = np.asarray(m.indptr, dtype=np.int64), np.asarray(m.indices, dtype=np.int64)
+        nnz = int(rowptr[-1])
+        if rowptr.size != nrows + 1 or rowptr[0] != 0 or np.any(np.diff(rowptr) < 0) or colind.size < nnz \
+                or m.data.size < nnz or (nnz and (colind[:nnz].min() < 0 or colind[:nnz].max() >= ncols)):
+            raise ValueError('DeviceCSR: inconsistent CSR arrays')
+        self.shape, self.nnz, self.dtype = (int(nrows), int(ncols)), nnz, dtype
+        self.lanes = spmv_lanes(nnz, nrows)
+        dev = device()
+        plan = spmv_plan(rowptr)
+        self.rowptr = torch.as_tensor(rowptr).to(dev)
+        self.colind = torch.as_tensor(colind[:nnz].astype(np.int32)).to(dev)
+        self.vals = torch.as_tensor(np.asarray(m.data[:nnz]).real.astype(np.float64)).to(device=dev, dtype=dtype)
+        self.chunk_row, self.chunk_start, self.long_row, self.long_first = (torch.as_tensor(a).to(dev) for a in plan)
+        self.nchunks, self.nlong = int(plan[0].size), int(plan[2].size)
+        self.partials = torch.empty(max(self.nchunks, 1), dtype=torch.float64, device=dev)
+
+
+def spmv(A, x, out=None, lanes=None):
+    """``A x`` for a ``DeviceCSR`` (``pcs_csr_spmv``); ``lanes`` overrides the matrix's lanes per row."""
+    lib = L.gpu()
+    nrows, ncols = A.shape
+    out = torch.empty(nrows, dtype=A.dtype, device=x.device) if out is None else out
+    if x.dtype != A.dtype or out.dtype != A.dtype or x.numel() != ncols or out.numel() != nrows \
+            or not _dense_on(A.vals.device, x, out):
+        raise ValueError(f'spmv: x and out must be contiguous {A.dtype} tensors of {ncols} and {nrows} elements on '
+                         f'{A.vals.device}')
+    L.check(lib.pcs_csr_spmv(L.dtcode(x), nrows, ncols, A.nnz, L.ptr(A.rowptr), L.ptr(A.colind), L.ptr(A.vals),
+                             L.ptr(x), L.ptr(out), A.lanes if lanes is None else int(lanes), A.nchunks,
+                             L.ptr(A.chunk_row), L.ptr(A.chunk_start), A.nlong, L.ptr(A.long_row),
+                             L.ptr(A.long_first), L.ptr(A.partials), L.stream()), 'pcs_csr_spmv')
+    return out
+
+
+def _pool_call(fn, name, x, dims, block, scale, n_out):
+    dims, block = [int(d) for d in dims], [int(b) for b in block]
+    if len(dims) != len(block) or not 1 <= len(dims) <= 3:
+        raise ValueError(f'{name}: 1 to 3 axes with one block size each')
+    if not _dense_on(x.device, x):
+        raise ValueError(f'{name}: the input must be a contiguous tensor on a GPU')
+    out = torch.empty(n_out, dtype=x.dtype, device=x.device)
+    L.check(fn(L.dtcode(x), L.ptr(x), L.ptr(out), len(dims), L.i64s(dims), L.i64s(block), float(scale), L.stream()),
+            name)
+    return out
+
+
+def pooled_shape(dims, block):
+    return tuple(-(-int(d) // int(b)) for d, b in zip(dims, block))
+
+
+def pool(x, dims, block, scale=1.0):
+    """``scale`` times the block sums of a C-order array of shape ``dims`` (1 to 3 axes), ragged blocks zero
+    padded (``pcs_pool_fwd``)."""
+    if x.numel() != int(np.prod(dims)):
+        raise ValueError('pool: x must have prod(dims) elements')
+    n_out = int(np.prod(pooled_shape(dims, block)))
+    return _pool_call(L.gpu().pcs_pool_fwd, 'pcs_pool_fwd', x, dims, block, scale, n_out)
+
+
+def unpool(y, dims, block, scale=1.0):
+    """``out[p] = scale * y[block of p]`` for the unpooled shape ``dims`` (``pcs_pool_adj``)."""
+    if y.numel() != int(np.prod(pooled_shape(dims, block))):
+        raise ValueError('unpool: y must have one element per block')
+    return _pool_call(L.gpu().pcs_pool_adj, 'pcs_pool_adj', y, dims, block, scale, int(np.prod(dims)))
+
+
 def lap(x, dims, weights, steps, edge, adjoint=False):
     lib = L.gpu()
     out = torch.empty_like(x)

@@ -5,13 +5,16 @@
 scalar factors of the algebra; ``DenseLinearOperator`` (``base.py:102-118``) backs the
 LASSO problem (C1); ``LinOpStack`` / ``LinOpVStack`` / ``LinOpHStack`` (``base.py:159-302``)
 build stacked K operators (notebook cell [62]: ``K = LinOpVStack(Gop, D)``);
-``PolynomialLinearOperator`` (``base.py:636-700``) backs ``GeneralisedLaplacian``.
-Sparse / Dask / Kronecker operators are out of scope for this build.
+``PolynomialLinearOperator`` (``base.py:636-700``) backs ``GeneralisedLaplacian``;
+``SparseLinearOperator`` (``base.py:121-137``) holds a SciPy sparse matrix and applies it and its
+transpose with the CSR kernel ``pcs_csr_spmv`` (``csrc/spmv.hip``).  Dask / Kronecker / Khatri-Rao /
+Block operators are out of scope for this build.
 """
 
 from numbers import Number
 
 import numpy as np
+import scipy.sparse as sparse
 import torch
 
 from .. import _ops as O
@@ -20,19 +23,38 @@ from ..core.map import DiffMapStack
 
 
 class ExplicitLinearOperator(LinearOperator):
-    """Operator given by an explicit dense matrix, held in HBM (``base.py:57-99``)."""
+    """Operator given by an explicit matrix held in HBM (``base.py:57-99``): a dense array, or anything
+    ``scipy.sparse.issparse`` accepts.  A sparse matrix stays in ``.mat`` as given; its CSR form with sorted
+    indices, and on the first adjoint the CSR of its transpose (``mat.T.tocsr()``, sorted), are built once on the
+    host and cached on the device per dtype, with their long-row chunk lists and workspaces."""
 
     def __init__(self, array, is_symmetric=False):
+        is_sparse = sparse.issparse(array)
         if isinstance(array, torch.Tensor):
             dt = np.float32 if array.dtype == torch.float32 else np.float64
-        elif isinstance(array, np.ndarray):
+        elif isinstance(array, np.ndarray) or is_sparse:
             dt = array.dtype
         else:
             raise TypeError('Invalid input type.')
-        super().__init__(shape=tuple(array.shape), dtype=dt, is_explicit=True, is_dask=False, is_dense=True,
-                         is_sparse=False, is_symmetric=is_symmetric)
+        super().__init__(shape=tuple(array.shape), dtype=dt, is_explicit=True, is_dask=False, is_dense=not is_sparse,
+                         is_sparse=is_sparse, is_symmetric=is_symmetric)
         self.mat = array
         self._dev = {}
+        self._host_csr = {}
+
+    def _csr(self, dtype, transposed):
+        """The device CSR of ``mat`` (or of its transpose) in ``dtype``."""
+        A = self._dev.get((dtype, transposed))
+        if A is None:
+            h = self._host_csr.get(transposed)
+            if h is None:
+                h = (self.mat.T if transposed else self.mat).tocsr()
+                if not h.has_sorted_indices:
+                    h = h.sorted_indices()      # a copy: ``mat`` is the caller's
+                self._host_csr[transposed] = h
+            A = self._dev[(dtype, transposed)] = O.DeviceCSR(h, dtype)
+        return A
+
 
     def _m(self, dtype):
         m = self._dev.get(dtype)
@@ -43,9 +65,13 @@ class ExplicitLinearOperator(LinearOperator):
         return m
 
     def _apply(self, t):
+        if self.is_sparse:
+            return O.spmv(self._csr(t.dtype, False), t)
         return torch.mv(self._m(t.dtype), t)
 
     def _adj(self, t):
+        if self.is_sparse:
+            return O.spmv(self._csr(t.dtype, True), t)
         return torch.mv(self._m(t.dtype).T, t)
 
 
@@ -54,6 +80,13 @@ class DenseLinearOperator(ExplicitLinearOperator):
 
     def __init__(self, ndarray, is_symmetric=False):
         super().__init__(array=ndarray, is_symmetric=is_symmetric)
+
+
+class SparseLinearOperator(ExplicitLinearOperator):
+    """``base.py:121-137``: the operator of a SciPy sparse matrix (``is_sparse=True``, ``is_dense=False``)."""
+
+    def __init__(self, spmatrix, is_symmetric=False):
+        super().__init__(array=spmatrix, is_symmetric=is_symmetric)
 
 
 class DiagonalOperator(LinearOperator):
