@@ -246,7 +246,7 @@ def bound(p, nit=1, dtype=None):
 
 
 def compare(got, ref, bound, shape, name='x', diag=None, diag_ref=None, dtype=None):
-    """Assert max |got - ref| <= bound.tol element-wise; on failure name the worst element: (row, col), for
+    """Assert max |got - ref| <= bound.tol element-wise; on failure name the worst element: (row, col), or (plane, row, col) when `shape` has three entries, for
     a dual variable its component, the error in units of eps * M, the column modulo 64.  With `diag`
     (the solver's diagnostics frame) and `diag_ref` (the oracle's): every row, the first included, is finite
     and within 1e-3 (fp32) / 1e-9 (fp64) relative.  Returns the worst error in units of eps * M."""
@@ -259,11 +259,15 @@ def compare(got, ref, bound, shape, name='x', diag=None, diag_ref=None, dtype=No
     i = int(np.argmax(err))
     worst = float(err[i])
     if worst > tol:
-        n0, n1 = shape
-        comp, pix = divmod(i, n0 * n1)
+        n1 = int(shape[-1])  # (rows, cols), or (planes, rows, cols) for a volume
+        comp, pix = divmod(i, int(np.prod(shape)))
         row, col = divmod(pix, n1)
+        where = f'row {row}, col {col}'
+        if len(shape) == 3:
+            plane, row = divmod(row, int(shape[1]))
+            where = f'plane {plane}, row {row}, col {col}'
         raise AssertionError(
-            f'{name}: |got - ref| = {worst:.3e} > {tol:.3e} at (row {row}, col {col}), component {comp}: '
+            f'{name}: |got - ref| = {worst:.3e} > {tol:.3e} at ({where}), component {comp}: '
             f'{worst / unit:.1f} eps*M (bound {tol / unit:.0f}), col % 64 = {col % 64}, got {got[i]!r}, ref {ref[i]!r}; '
             f'{int(np.sum(err > tol))} elements over the bound')
     if diag is not None:
