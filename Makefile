@@ -6,6 +6,8 @@ HDR := $(wildcard pycsou_amd/csrc/*.hpp) include/pycsou_hip.h
 LIB := pycsou_amd/lib/libpycsou_hip.so
 OBJ := $(patsubst pycsou_amd/csrc/%.hip,build/%.o,$(SRC))
 FLAGS := --offload-arch=$(ARCH) -O3 -fno-slp-vectorize -fPIC -std=c++17 -Wall -Wno-unused-function -Iinclude
+# mcmc.hip: running sums and P2 markers must round as NumPy does (no a*b+c -> fma)
+FLAGS_mcmc := -ffp-contract=off
 
 all: $(LIB)
 

@@ -346,6 +346,55 @@ int pcs_apgd_step(int dtype, const void* x, const void* g, const void* aux, void
                   double tau, double a, int gkind, double lam, double seg_a, double seg_b, double* sums_dev,
                   void* ws, hipStream_t stream);
 
+/* ---------------------------------------------------------------- PMYULA sampler, P2 streaming quantiles */
+
+/* State of K <= PCS_P2_MAX_K P-square estimators (pycsou/util/stats.py) over n pixels, structure of arrays:
+ *   heights[K][5][n]  marker heights in `dtype`, ascending over the middle index
+ *   pos[K][3][n]      int32 positions of markers 1..3 (marker 0 is at 1, marker 4 at `count`)
+ * `count` is the number of samples including the one being added (1 <= count < 2^31).  Samples 1..5 are the
+ * warm-up (sorted insertion; sample 5 sets the positions to 1..5); from the sixth on `desired` (host, 5
+ * doubles per p-value: the desired marker positions after this sample's increment, accumulated by repeated
+ * addition as P2Algorithm.add_sample does) is passed to the kernel by value.  The update follows
+ * stats.py:97-132 operation for operation, uncontracted, so fp64 states equal the reference's bit for bit.
+ * Any n; 16-B accesses when n is a multiple of 16 / sizeof(dtype) and the arrays are 16-B aligned.
+ * PCS_EINVAL: null pointer, n < 0, K outside 1..PCS_P2_MAX_K (0 allowed for pcs_mcmc_accumulate), bad dtype. */
+#define PCS_P2_MAX_K 8
+int pcs_p2_update(int dtype, const void* x, void* heights, int32_t* pos, int64_t n, int K, int64_t count,
+                  const double* desired, hipStream_t stream);
+/* Host-only twin of pcs_p2_update (the same __host__ __device__ element update) on host arrays. */
+int pcs_p2_update_host(int dtype, const void* x, void* heights, int32_t* pos, int64_t n, int K, int64_t count,
+                       const double* desired);
+/* One retained sample of PMYULA (pycsou/opt/mcmc.py:125-129 and 197-208), reading x once:
+ *   sums_dev[0] = sum x^2, sums_dev[1] = sum S_old^2   (fp64, fixed order, no atomics: the reference's
+ *                 diagnostic ||old_sum - new_sum|| / ||old_sum||, the difference being x)
+ *   sum += x ; sumsq += x * x ; the K P2 states take x (K = 0: no quantiles, heights / pos / desired unused).
+ * ws >= pcs_reduce_ws_bytes().  x, sum and sumsq are distinct arrays. */
+int pcs_mcmc_accumulate(int dtype, const void* x, void* sum, void* sumsq, void* heights, int32_t* pos, int64_t n,
+                        int K, int64_t count, const double* desired, double* sums_dev, void* ws, hipStream_t stream);
+
+/* One Langevin step (mcmc.py:112-118) with g = grad F(x), summed left to right:
+ *   PCS_MYULA_P_NONE  xn = (x - gamma g) + sqrt(2 gamma) z                                  (G null, mcmc.py:114)
+ *   otherwise         xn = (((1 - gamma/tau) x - gamma g) + (gamma/tau) p) + sqrt(2 gamma) z
+ *     PCS_MYULA_P_BUF   p read from the buffer `p` (= G.prox(x, tau) computed by the caller)
+ *     PCS_MYULA_P_KIND  p = G.prox(x, tau) in the kernel, gkind as in pcs_apgd_step (PCS_G_NULL: p = x)
+ * z: a buffer of n normals, or NULL for in-kernel noise: Philox4x32-10 with key (seed low, seed high) and
+ * counter (element / 4, iter, stream_id, 0), Box-Muller in fp32 on 24-bit uniforms (the mapping is stated in
+ * csrc/mcmc_core.hpp and is part of this contract); the value of an element depends on seed, iter, stream_id
+ * and its index alone.  xn aliases no input. */
+enum { PCS_MYULA_P_NONE = 0, PCS_MYULA_P_BUF = 1, PCS_MYULA_P_KIND = 2 };
+int pcs_myula_step(int dtype, const void* x, const void* g, const void* p, const void* z, void* xn, int64_t n,
+                   double tau, double gamma, int pmode, int gkind, double lam, double seg_a, double seg_b,
+                   uint64_t seed, uint32_t iter, uint32_t stream_id, hipStream_t stream);
+/* out[0..n) = the normals pcs_myula_step generates for (seed, iter, stream_id), in `dtype`. */
+int pcs_mcmc_normal(int dtype, void* out, int64_t n, uint64_t seed, uint32_t iter, uint32_t stream_id,
+                    hipStream_t stream);
+/* out[4 b .. 4 b + 3] = the raw Philox words of block b < nblocks for (seed, iter, stream_id). */
+int pcs_mcmc_philox(uint32_t* out, int64_t nblocks, uint64_t seed, uint32_t iter, uint32_t stream_id,
+                    hipStream_t stream);
+/* Host-only twins (no GPU): one Philox4x32-10 block, and the fp32 normals of pcs_mcmc_normal. */
+int pcs_mcmc_philox_host(const uint32_t* ctr, const uint32_t* key, uint32_t* out);
+int pcs_mcmc_normal_host(uint64_t seed, uint32_t iter, uint32_t stream_id, int64_t n, float* out);
+
 /* ---------------------------------------------------------------- fused PDS iteration */
 
 /* One fused PrimalDualSplitting.update_iterand + update_diagnostics

@@ -20,6 +20,8 @@ PCS_H_L1, PCS_H_L21 = 0, 1
 PCS_K_GRAD_FORWARD, PCS_K_GRAD_BACKWARD, PCS_K_GRAD_CENTERED, PCS_K_LAPLACIAN = 0, 1, 2, 3
 PCS_G_NULL, PCS_G_NONNEG, PCS_G_SEGMENT = 0, 1, 2
 PCS_APGD_G_L1 = 3
+PCS_P2_MAX_K = 8
+PCS_MYULA_P_NONE, PCS_MYULA_P_BUF, PCS_MYULA_P_KIND = 0, 1, 2
 PCS_THRESH_SOFT, PCS_THRESH_CLIP = 0, 1
 PCS_THRESH_PIVOTS = 31
 # pcs_cumsum: shortest segment of a split line (contiguous / strided layout) and the workspace bound
@@ -171,6 +173,15 @@ _SIGS = {
     'pcs_reduce': (_c_int, [_c_int, _c_int, _vp, _vp, _c_i64, _vp, _vp, _vp]),
     'pcs_apgd_step': (_c_int, [_c_int, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_dbl, _c_dbl, _c_int, _c_dbl, _c_dbl,
                                 _c_dbl, _vp, _vp, _vp]),
+    'pcs_p2_update': (_c_int, [_c_int, _vp, _vp, _vp, _c_i64, _c_int, _c_i64, _pdbl, _vp]),
+    'pcs_p2_update_host': (_c_int, [_c_int, _vp, _vp, _vp, _c_i64, _c_int, _c_i64, _pdbl]),
+    'pcs_mcmc_accumulate': (_c_int, [_c_int, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_int, _c_i64, _pdbl, _vp, _vp, _vp]),
+    'pcs_myula_step': (_c_int, [_c_int, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_dbl, _c_dbl, _c_int, _c_int, _c_dbl,
+                                 _c_dbl, _c_dbl, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp]),
+    'pcs_mcmc_normal': (_c_int, [_c_int, _vp, _c_i64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp]),
+    'pcs_mcmc_philox': (_c_int, [_vp, _c_i64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp]),
+    'pcs_mcmc_philox_host': (_c_int, [_vp, _vp, _vp]),
+    'pcs_mcmc_normal_host': (_c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _c_i64, _vp]),
     'pcs_pds2d_halo_x': (_c_int, [_c_int]),
     'pcs_pds2d_ntaps_len': (_c_int, [_c_int]),
     'pcs_pds2d_nblocks': (_c_i64, [ctypes.POINTER(PdsArgs)]),

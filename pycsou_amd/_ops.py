@@ -148,6 +148,111 @@ def apgd_step(x, g, aux, tau, a, gkind, lam=1.0, seg=(0.0, 1.0), sums=None):
     return xn, auxn, sums
 
 
+def myula_step(x, g, tau, gamma, p=None, gk=None, z=None, seed=0, it=0, stream_id=0, out=None):
+    """One Langevin step (``pcs_myula_step``).  ``p``: G.prox(x, tau) as a buffer; else ``gk`` = (kind, lam, seg)
+    of ``engine.apgd_g_kind`` for a prox formed in the kernel; neither: the G-null form.  ``z``: the normals, or
+    None for in-kernel Philox noise keyed by (seed, it, stream_id)."""
+    lib = L.gpu()
+    out = torch.empty_like(x) if out is None else out
+    mode, kind, lam, seg = L.PCS_MYULA_P_NONE, 0, 1.0, (0.0, 1.0)
+    if p is not None:
+        mode = L.PCS_MYULA_P_BUF
+    elif gk is not None:
+        mode, (kind, lam, seg) = L.PCS_MYULA_P_KIND, gk
+    for t in (g, p, z):
+        if t is not None and (t.dtype != x.dtype or t.numel() != x.numel() or not _dense_on(x.device, t)):
+            raise ValueError('myula_step: every buffer must be a contiguous tensor of the dtype, size and GPU of x')
+    L.check(lib.pcs_myula_step(L.dtcode(x), L.ptr(x), L.ptr(g), L.ptr(p), L.ptr(z), L.ptr(out), x.numel(),
+                               float(tau if tau is not None else 0.0), float(gamma), mode, int(kind), float(lam),
+                               float(seg[0]), float(seg[1]), int(seed) & (2 ** 64 - 1), int(it) & 0xffffffff,
+                               int(stream_id) & 0xffffffff, L.stream()), 'pcs_myula_step')
+    return out
+
+
+def mcmc_normal(n, dtype, seed, it, stream_id=0):
+    """The n normals ``pcs_myula_step`` generates for (seed, it, stream_id), as a device tensor."""
+    lib = L.gpu()
+    out = torch.empty(int(n), dtype=dtype, device=device())
+    L.check(lib.pcs_mcmc_normal(L.dtcode(out), L.ptr(out), out.numel(), int(seed) & (2 ** 64 - 1),
+                                int(it) & 0xffffffff, int(stream_id) & 0xffffffff, L.stream()), 'pcs_mcmc_normal')
+    return out
+
+
+def mcmc_philox(nblocks, seed, it, stream_id=0):
+    """Raw Philox words of blocks 0..nblocks-1 (4 per block) as an int32 device tensor (bit patterns)."""
+    lib = L.gpu()
+    out = torch.empty(4 * int(nblocks), dtype=torch.int32, device=device())
+    L.check(lib.pcs_mcmc_philox(L.ptr(out), int(nblocks), int(seed) & (2 ** 64 - 1), int(it) & 0xffffffff,
+                                int(stream_id) & 0xffffffff, L.stream()), 'pcs_mcmc_philox')
+    return out
+
+
+class P2State:
+    """Device state of K P-square estimators over n pixels (layout of ``pcs_p2_update``): ``heights`` (K, 5, n)
+    in ``dtype``, ``pos`` (K, 3, n) int32 for markers 1..3, and on the host the sample count and the desired
+    positions, accumulated by repeated addition as ``P2Algorithm.add_sample`` does."""
+
+    def __init__(self, pvalues, n, dtype, dev=None):
+        self.pvalues = tuple(float(p) for p in pvalues)
+        self.K, self.n, self.count = len(self.pvalues), int(n), 0
+        if self.K > L.PCS_P2_MAX_K:
+            raise ValueError(f'at most {L.PCS_P2_MAX_K} p-values per state, got {self.K}')
+        dev = device() if dev is None else dev
+        self.heights = torch.zeros((max(self.K, 1), 5, self.n), dtype=dtype, device=dev)
+        self.pos = torch.zeros((max(self.K, 1), 3, self.n), dtype=torch.int32, device=dev)
+        self.desired, self.increments = p2_desired(self.pvalues)
+
+    def advance(self):
+        """Count one more sample; returns the desired positions to pass with it."""
+        self.count += 1
+        if self.count > 5:
+            self.desired += self.increments  # stats.py:91
+        return self.desired
+
+    def add(self, x):
+        """``pcs_p2_update`` with the sample ``x`` (device tensor of n elements)."""
+        lib = L.gpu()
+        if x.dtype != self.heights.dtype or x.numel() != self.n or not _dense_on(self.heights.device, x):
+            raise ValueError('P2State.add: the sample must be a contiguous tensor of the state\'s dtype, size and GPU')
+        des = np.ascontiguousarray(self.advance())
+        L.check(lib.pcs_p2_update(L.dtcode(x), L.ptr(x), L.ptr(self.heights), L.ptr(self.pos), self.n, self.K,
+                                  self.count, des.ctypes.data_as(L._pdbl), L.stream()), 'pcs_p2_update')
+
+    def quantile(self, k):
+        """Marker 2 of estimator k (``P2Algorithm.q``): None before the sixth sample."""
+        return None if self.count <= 5 else self.heights[k, 2]
+
+    def positions(self, k):
+        """(n, 5) marker positions of estimator k as the reference keeps them, None before the fifth sample."""
+        if self.count < 5:
+            return None
+        p = self.pos[k].to(torch.int64)
+        ends = torch.ones(self.n, dtype=torch.int64, device=p.device)
+        return torch.stack([ends, p[0], p[1], p[2], ends * self.count], dim=1)
+
+
+def p2_desired(pvalues):
+    """Initial desired marker positions and their increments, (K, 5) float64 each (stats.py:67-68)."""
+    des = np.array([[1, 1 + 2 * p, 1 + 4 * p, 3 + 2 * p, 5] for p in pvalues], dtype=np.float64).reshape(-1, 5)
+    inc = np.array([[0, p / 2, p, (p + 1) / 2, 1] for p in pvalues], dtype=np.float64).reshape(-1, 5)
+    return des, inc
+
+
+def mcmc_accumulate(x, total, total_sq, state, sums):
+    """One retained sample (``pcs_mcmc_accumulate``): ``total += x``, ``total_sq += x * x``, the P2 ``state``
+    takes x, and ``sums[0..1]`` (float64 device slice) = sum x^2, sum total_old^2."""
+    lib = L.gpu()
+    for t in (total, total_sq):
+        if t.dtype != x.dtype or t.numel() != x.numel() or not _dense_on(x.device, t):
+            raise ValueError('mcmc_accumulate: the sums must be contiguous tensors of the dtype, size and GPU of x')
+    if state.n != x.numel() or state.heights.dtype != x.dtype or not _dense_on(x.device, x, state.heights, sums):
+        raise ValueError('mcmc_accumulate: the P2 state does not match the sample')
+    des = np.ascontiguousarray(state.advance())
+    L.check(lib.pcs_mcmc_accumulate(L.dtcode(x), L.ptr(x), L.ptr(total), L.ptr(total_sq), L.ptr(state.heights),
+                                    L.ptr(state.pos), x.numel(), state.K, state.count, des.ctypes.data_as(L._pdbl),
+                                    L.ptr(sums), L.ptr(_ws(x)), L.stream()), 'pcs_mcmc_accumulate')
+
+
 def sumsq(x):
     return float(reduce_dev(0, x).item())
 
