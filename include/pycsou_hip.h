@@ -224,6 +224,45 @@ int pcs_csr_spmv(int dtype, int64_t nrows, int64_t ncols, int64_t nnz, const int
                  const int64_t* chunk_start, int64_t nlong, const int64_t* long_row, const int64_t* long_first,
                  void* partials, hipStream_t stream);
 
+/* CSR matrix times a row-major dense matrix along one of its axes (csrc/spmm.hip; the sparse factors of
+ * KroneckerProduct / KroneckerSum, pycsou/linop/base.py:715-886).  A and its chunk lists are those of
+ * pcs_csr_spmv; nb is the length of the other axis of X.
+ *   axis 0:  out (nrows x nb) = A X,    X (ncols x nb): min(64, nb rounded up to a power of two) lanes across the columns of one row,
+ *            each walking the row's entries in order (rows of any length; the chunk lists are not used).
+ *   axis 1:  out (nb x nrows) = X A^T,  X (nb x ncols): the kernels of pcs_csr_spmv with the batch on grid y;
+ *            partials holds nb * nchunks doubles (partials_len >= that), batch row b the bits of pcs_csr_spmv.
+ *   nb == 1: either axis is that vector product, bit for bit pcs_csr_spmv (and needs its partials).
+ * accumulate = 1: out = out + ..., rounded once ((T)((double)out + sum)).  Sums in fp64, no atomics, every order
+ * a function of (rowptr, lanes, axis, nb == 1) alone.  PCS_EINVAL before any device call for what pcs_csr_spmv
+ * rejects, an axis or accumulate outside {0, 1}, a negative nb, a partials workspace too small for nb rows, or
+ * out overlapping X.  nrows == 0 or nb == 0 is an empty product (0, no launch). */
+int pcs_csr_spmm(int dtype, int axis, int accumulate, int64_t nrows, int64_t ncols, int64_t nnz, const int64_t* rowptr,
+                 const int32_t* colind, const void* vals, const void* X, void* out, int64_t nb, int lanes,
+                 int64_t nchunks, const int64_t* chunk_row, const int64_t* chunk_start, int64_t nlong,
+                 const int64_t* long_row, const int64_t* long_first, void* partials, int64_t partials_len,
+                 hipStream_t stream);
+
+/* Khatri-Rao product of two dense row-major factors A (k x l) and B (n x l) (csrc/khatri_rao.hip;
+ * KhatriRaoProduct, pycsou/linop/base.py:889-989):
+ *   pcs_khatri_rao_fwd:  out (n x k, row-major) = (B * x[None, :]) A^T
+ *   pcs_khatri_rao_adj:  out[c] = B[:, c]^T Y A[:, c],  Y (n x k, row-major)
+ * for k * n <= PCS_KR_MAX_NK and k + n <= PCS_KR_MAX_ROWS (the LDS and register budget derived in the source
+ * file); the caller composes larger products.  The forward cuts the l columns into slabs of PCS_KR_SLAB;
+ * workgroup g of `ngroups` = ceil(nslabs / spg) <= PCS_KR_MAX_GROUPS sums `spg` consecutive slabs in column
+ * order into partials[g * n k ..] (ngroups * n * k doubles, partials_len >= that), and a second kernel adds the
+ * groups in order.  Sums in fp64, rounded once, no atomics; the bits depend on (k, n, l, spg) alone.
+ * PCS_EINVAL before any device call for an unknown dtype, a negative size, a shape past the limits, a plan that
+ * does not tile l, a null or misaligned or short workspace, a null array, or out overlapping an input. */
+#define PCS_KR_SLAB 64
+#define PCS_KR_MAX_NK 1024
+#define PCS_KR_MAX_ROWS 120
+#define PCS_KR_MAX_GROUPS 512
+int pcs_khatri_rao_fwd(int dtype, const void* A, const void* B, const void* x, void* out, int64_t k, int64_t n,
+                       int64_t l, int64_t spg, int64_t ngroups, void* partials, int64_t partials_len,
+                       hipStream_t stream);
+int pcs_khatri_rao_adj(int dtype, const void* A, const void* B, const void* Y, void* out, int64_t k, int64_t n,
+                       int64_t l, hipStream_t stream);
+
 /* Block pooling of a C-order array of ndim in 1..3 axes (Pooling, pycsou/linop/sampling.py:394-536 ->
  * skimage.measure.block_reduce with cval = 0) and its unpooling (Pooling.adjoint, np.repeat and crop).
  * dims[ndim] is the shape of the UNPOOLED array in both calls, block[ndim] >= 1 the block sizes; the pooled

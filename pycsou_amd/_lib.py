@@ -29,6 +29,8 @@ PCS_CUMSUM_SPAN, PCS_CUMSUM_SPAN_STRIDED = 2048, 64
 PCS_CUMSUM_WS_MAX = 2 * 1024 * 1024 + 64 * 1024
 # pcs_csr_spmv: rows of more than LONG_ROW entries are cut into chunks of CHUNK entries
 PCS_SPMV_LONG_ROW, PCS_SPMV_CHUNK = 4096, 4096
+# pcs_khatri_rao_*: column slab, the fused limits k n <= MAX_NK and k + n <= MAX_ROWS, most workgroups of the forward
+PCS_KR_SLAB, PCS_KR_MAX_NK, PCS_KR_MAX_ROWS, PCS_KR_MAX_GROUPS = 64, 1024, 120, 512
 PCS_F_NULL, PCS_F_DENOISE, PCS_F_SEPCONV, PCS_F_GRADBUF, PCS_F_CONV2D, PCS_F_CONV0 = 0, 1, 2, 3, 4, 5
 PCS_M_NONE, PCS_M_L1LOSS = 0, 1
 # pcs_pds2d_path: the kernel family of a fused 2-D step
@@ -123,6 +125,11 @@ _SIGS = {
     'pcs_gather_or_zero': (_c_int, [_c_int, _vp, _vp, _vp, _c_i64, _vp]),
     'pcs_csr_spmv': (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_int, _c_i64, _vp, _vp, _c_i64,
                               _vp, _vp, _vp, _vp]),
+    'pcs_csr_spmm': (_c_int, [_c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_int,
+                              _c_i64, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _vp]),
+    'pcs_khatri_rao_fwd': (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _c_i64,
+                                    _vp]),
+    'pcs_khatri_rao_adj': (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _vp]),
     'pcs_pool_fwd': (_c_int, [_c_int, _vp, _vp, _c_int, _pi64, _pi64, _c_dbl, _vp]),
     'pcs_pool_adj': (_c_int, [_c_int, _vp, _vp, _c_int, _pi64, _pi64, _c_dbl, _vp]),
     'pcs_grad_fwd': (_c_int, [_c_int, _vp, _vp, _c_int, _pi64, _pdbl, _c_int, _c_int, _vp]),

@@ -574,6 +574,113 @@ def spmv(A, x, out=None, lanes=None):
     return out
 
 
+def spmm_plan(A, axis, nb):
+    """Launch and workspace plan of pcs_csr_spmm for a ``DeviceCSR``-like ``A`` (``shape``, ``nchunks``): the
+    kernel family ('cols': lanes across the nb columns, entries in order; 'rows': the pcs_csr_spmv scheme with
+    the batch on grid y), the lanes across the columns, and the doubles of the partials workspace."""
+    nb = int(nb)
+    if axis not in (0, 1) or nb < 0:
+        raise ValueError('spmm: axis is 0 or 1 and nb >= 0')
+    if axis == 0 and nb > 1:
+        width = 1
+        while width < 64 and width < nb:
+            width *= 2
+        return {'family': 'cols', 'width': width, 'col_tiles': -(-nb // width), 'partials': 0}
+    return {'family': 'rows', 'width': 0, 'col_tiles': 0, 'partials': nb * int(A.nchunks)}
+
+
+def spmm(A, X, axis, out=None, accumulate=False):
+    """``A X`` (axis 0, ``X`` of shape (ncols, nb)) or ``X A^T`` (axis 1, ``X`` of shape (nb, ncols)) for a
+    ``DeviceCSR`` and a contiguous 2-D tensor (``pcs_csr_spmm``); ``accumulate`` adds the product to ``out``.  The
+    partials workspace of the long rows is kept on ``A`` per batch size, so a captured loop replays with it."""
+    lib = L.gpu()
+    nrows, ncols = A.shape
+    if X.dim() != 2 or axis not in (0, 1) or X.shape[axis] != ncols or X.dtype != A.dtype:
+        raise ValueError(f'spmm: X must be a 2-D {A.dtype} tensor with {ncols} entries along axis {axis}')
+    nb = int(X.shape[1 - axis])
+    shape = (nrows, nb) if axis == 0 else (nb, nrows)
+    if out is None:
+        if accumulate:
+            raise ValueError('spmm: accumulate needs out')
+        out = torch.empty(shape, dtype=A.dtype, device=X.device)
+    if tuple(out.shape) != shape or out.dtype != A.dtype or not _dense_on(A.vals.device, X, out):
+        raise ValueError(f'spmm: X and out must be contiguous {A.dtype} tensors on {A.vals.device}, out of shape {shape}')
+    need = spmm_plan(A, axis, nb)['partials']
+    ws = A.partials
+    if need > ws.numel():
+        cache = A.__dict__.setdefault('spmm_partials', {})
+        ws = cache.get(nb)
+        if ws is None:
+            ws = cache[nb] = torch.empty(need, dtype=torch.float64, device=A.vals.device)
+    L.check(lib.pcs_csr_spmm(L.dtcode(X), int(axis), int(bool(accumulate)), nrows, ncols, A.nnz, L.ptr(A.rowptr),
+                             L.ptr(A.colind), L.ptr(A.vals), L.ptr(X), L.ptr(out), nb, A.lanes, A.nchunks,
+                             L.ptr(A.chunk_row), L.ptr(A.chunk_start), A.nlong, L.ptr(A.long_row),
+                             L.ptr(A.long_first), L.ptr(ws), ws.numel(), L.stream()), 'pcs_csr_spmm')
+    return out
+
+
+# pcs_khatri_rao_*: the fused pair serves k n <= KR_MAX_NK and k + n <= KR_MAX_ROWS (derived in csrc/khatri_rao.hip)
+KR_SLAB, KR_MAX_NK, KR_MAX_ROWS, KR_MAX_GROUPS = L.PCS_KR_SLAB, L.PCS_KR_MAX_NK, L.PCS_KR_MAX_ROWS, L.PCS_KR_MAX_GROUPS
+
+
+def kr_fused_ok(k, n):
+    """Whether the fused Khatri-Rao kernels serve factors of k and n rows."""
+    return 1 <= k and 1 <= n and k * n <= KR_MAX_NK and k + n <= KR_MAX_ROWS
+
+
+# Measured on an MI355X (profiles/kron_bench.jsonl, DESIGN 5.4): the fused forward beats mm(B * x, A^T) in every
+# class it serves; the fused adjoint beats sum(mm(Y, A) * B, 0) up to k n = 256 in both dtypes and, in fp64, up to
+# 32 x 32; with more rows in one factor (64 x 16, 100 x 10) and for 32 x 32 in fp32 the composition is faster.
+KR_ADJ_FUSED_MAX_NK, KR_ADJ_FUSED_MAX_SIDE_F64 = 256, 32
+
+
+def kr_route(k, n, dtype, adjoint):
+    """'fused' or 'torch' for a dense Khatri-Rao pair of k and n rows: the derived limit first, then the measured
+    boundary of the adjoint."""
+    if not kr_fused_ok(k, n):
+        return 'torch'
+    if not adjoint or k * n <= KR_ADJ_FUSED_MAX_NK:
+        return 'fused'
+    if torch_dtype(dtype) == torch.float64 and max(k, n) <= KR_ADJ_FUSED_MAX_SIDE_F64:
+        return 'fused'
+    return 'torch'
+
+
+def kr_fwd_plan(k, n, l):
+    """Launch and workspace plan of pcs_khatri_rao_fwd: (slabs per workgroup, workgroups, doubles of partials).
+    The l columns make ceil(l / KR_SLAB) slabs; at most KR_MAX_GROUPS workgroups share them in runs of ``spg``."""
+    nslabs = -(-int(l) // KR_SLAB)
+    spg = max(1, -(-nslabs // KR_MAX_GROUPS))
+    ngroups = -(-nslabs // spg)
+    return spg, ngroups, max(ngroups * int(k) * int(n), 1)
+
+
+def khatri_rao_fwd(A, B, x, ws, out=None):
+    """``(B * x) A^T`` (shape (n, k)) for dense row-major device matrices A (k, l) and B (n, l); ``ws``: the
+    float64 partials workspace of ``kr_fwd_plan``."""
+    lib = L.gpu()
+    (k, l), n = A.shape, B.shape[0]
+    if B.shape[1] != l or x.numel() != l or not (A.dtype == B.dtype == x.dtype) or not _dense_on(A.device, A, B, x, ws):
+        raise ValueError('khatri_rao_fwd: A (k, l), B (n, l) and x (l) must be contiguous tensors of one dtype on one GPU')
+    spg, ngroups, _ = kr_fwd_plan(k, n, l)
+    out = torch.empty((n, k), dtype=A.dtype, device=A.device) if out is None else out
+    L.check(lib.pcs_khatri_rao_fwd(L.dtcode(A), L.ptr(A), L.ptr(B), L.ptr(x), L.ptr(out), k, n, l, spg, ngroups,
+                                   L.ptr(ws), ws.numel(), L.stream()), 'pcs_khatri_rao_fwd')
+    return out
+
+
+def khatri_rao_adj(A, B, Y, out=None):
+    """``out[c] = B[:, c]^T Y A[:, c]`` for dense row-major device matrices A (k, l), B (n, l) and Y of n k values."""
+    lib = L.gpu()
+    (k, l), n = A.shape, B.shape[0]
+    if B.shape[1] != l or Y.numel() != n * k or not (A.dtype == B.dtype == Y.dtype) or not _dense_on(A.device, A, B, Y):
+        raise ValueError('khatri_rao_adj: A (k, l), B (n, l) and Y (n k) must be contiguous tensors of one dtype on one GPU')
+    out = torch.empty(l, dtype=A.dtype, device=A.device) if out is None else out
+    L.check(lib.pcs_khatri_rao_adj(L.dtcode(A), L.ptr(A), L.ptr(B), L.ptr(Y), L.ptr(out), k, n, l, L.stream()),
+            'pcs_khatri_rao_adj')
+    return out
+
+
 def _pool_call(fn, name, x, dims, block, scale, n_out):
     dims, block = [int(d) for d in dims], [int(b) for b in block]
     if len(dims) != len(block) or not 1 <= len(dims) <= 3:

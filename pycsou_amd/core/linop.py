@@ -121,6 +121,35 @@ class LinearOperator(DifferentiableMap):
     def _jacT(self, t=None):
         return self.get_adjointOp()
 
+    def _apply_cols(self, T, axis, adjoint=False):
+        """The operator (or its adjoint) along ``axis`` of a contiguous 2-D device tensor: a contiguous result
+        with that axis replaced by the range dimension (the device counterpart of ``Map.apply_along_axis``).
+        The default is a loop over the lines on the device -- slice, ``_apply`` / ``_adj``, stack -- with no host
+        copy and no synchronisation; operators with a batched form override it."""
+        f = self._adj if adjoint else self._apply
+        n_out = self.shape[1] if adjoint else self.shape[0]
+        if axis == 0:
+            if T.shape[1] == 0:
+                return torch.empty((n_out, 0), dtype=T.dtype, device=T.device)
+            return torch.stack([f(T[:, j].contiguous()) for j in range(T.shape[1])], dim=1).contiguous()
+        if T.shape[0] == 0:
+            return torch.empty((0, n_out), dtype=T.dtype, device=T.device)
+        return torch.stack([f(T[i]) for i in range(T.shape[0])], dim=0)
+
+    def _apply_cols_acc(self, T, axis, adjoint, acc):
+        """``acc + _apply_cols(T, axis, adjoint)``; ``acc`` may be overwritten with the result."""
+        return O.add(acc, self._apply_cols(T, axis, adjoint))
+
+    def _apply_mid(self, T, adjoint=False):
+        """Along the middle axis of a contiguous (a, p, b) device tensor, through ``_apply_cols``."""
+        a, p, b = T.shape
+        if b == 1:
+            return self._apply_cols(T.reshape(a, p), 1, adjoint).reshape(a, -1, 1)
+        if a == 1:
+            return self._apply_cols(T.reshape(p, b), 0, adjoint).reshape(1, -1, b)
+        Z = self._apply_cols(T.permute(1, 0, 2).reshape(p, a * b), 0, adjoint)
+        return Z.reshape(-1, a, b).permute(1, 0, 2).contiguous()
+
     # -- public layer
     def matvec(self, x):
         return self.__call__(x)
@@ -252,6 +281,9 @@ class AdjointLinearOperator(LinearOperator):
     def _adj(self, t):
         return self.Linop._apply(t)
 
+    def _apply_cols(self, T, axis, adjoint=False):
+        return self.Linop._apply_cols(T, axis, not adjoint)
+
     def compute_lipschitz_cst(self, **kwargs):
         if self.Linop.lipschitz_cst != np.inf:
             self.lipschitz_cst = self.Linop.lipschitz_cst
@@ -282,6 +314,9 @@ class LinOpSum(LinearOperator, DiffMapSum):
     def _adj(self, t):
         return O.add(self.LinOp1._adj(t), self.LinOp2._adj(t))
 
+    def _apply_cols(self, T, axis, adjoint=False):
+        return self.LinOp2._apply_cols_acc(T, axis, adjoint, self.LinOp1._apply_cols(T, axis, adjoint))
+
 
 class LinOpComp(LinearOperator, DiffMapComp):
     """``linop.py:540-553``."""
@@ -301,6 +336,11 @@ class LinOpComp(LinearOperator, DiffMapComp):
 
     def _adj(self, t):
         return self.LinOp2._adj(self.LinOp1._adj(t))
+
+    def _apply_cols(self, T, axis, adjoint=False):
+        if adjoint:
+            return self.LinOp2._apply_cols(self.LinOp1._apply_cols(T, axis, True), axis, True)
+        return self.LinOp1._apply_cols(self.LinOp2._apply_cols(T, axis), axis)
 
     def _jacT(self, t=None):
         return self.get_adjointOp()
@@ -340,6 +380,9 @@ class SymmetricLinearOperator(LinearOperator):
 
     def _adj(self, t):
         return self.LinOp._apply(t)
+
+    def _apply_cols(self, T, axis, adjoint=False):
+        return self.LinOp._apply_cols(T, axis)
 
 
 class UnitaryOperator(LinearOperator):

@@ -7,8 +7,11 @@ LASSO problem (C1); ``LinOpStack`` / ``LinOpVStack`` / ``LinOpHStack`` (``base.p
 build stacked K operators (notebook cell [62]: ``K = LinOpVStack(Gop, D)``);
 ``PolynomialLinearOperator`` (``base.py:636-700``) backs ``GeneralisedLaplacian``;
 ``SparseLinearOperator`` (``base.py:121-137``) holds a SciPy sparse matrix and applies it and its
-transpose with the CSR kernel ``pcs_csr_spmv`` (``csrc/spmv.hip``).  Dask / Kronecker / Khatri-Rao /
-Block operators are out of scope for this build.
+transpose with the CSR kernel ``pcs_csr_spmv`` (``csrc/spmv.hip``).  ``KroneckerProduct`` / ``KroneckerSum`` /
+``KhatriRaoProduct`` (``base.py:715-989``) act through the device-side ``LinearOperator._apply_cols`` (an operator
+along one axis of a matrix: ``torch.matmul``, ``pcs_csr_spmm``, one stencil launch, or a column loop on the
+device) and, for two dense factors, the fused ``pcs_khatri_rao_*`` kernels (``csrc/khatri_rao.hip``);
+``BlockOperator`` / ``BlockDiagonalOperator`` (``base.py:339-548``) are stacks of the blocks.
 """
 
 from numbers import Number
@@ -74,6 +77,24 @@ class ExplicitLinearOperator(LinearOperator):
             return O.spmv(self._csr(t.dtype, True), t)
         return torch.mv(self._m(t.dtype).T, t)
 
+    def _apply_cols(self, T, axis, adjoint=False):
+        if self.is_sparse:
+            return O.spmm(self._csr(T.dtype, adjoint), T, axis)
+        M = self._m(T.dtype)
+        if axis == 0:
+            return torch.matmul(M.T if adjoint else M, T)
+        return torch.matmul(T, M if adjoint else M.T)
+
+    def _apply_cols_acc(self, T, axis, adjoint, acc):
+        if self.is_sparse:
+            if acc.data_ptr() == T.data_ptr():      # an identity term handed its input on: do not write into it
+                return O.add(acc, O.spmm(self._csr(T.dtype, adjoint), T, axis))
+            return O.spmm(self._csr(T.dtype, adjoint), T, axis, out=acc, accumulate=True)
+        M = self._m(T.dtype)
+        if axis == 0:
+            return torch.addmm(acc, M.T if adjoint else M, T)
+        return torch.addmm(acc, T, M if adjoint else M.T)
+
 
 class DenseLinearOperator(ExplicitLinearOperator):
     """``base.py:102-118``."""
@@ -117,6 +138,12 @@ class DiagonalOperator(LinearOperator):
     def _adj(self, t):
         return self._apply(t)
 
+    def _apply_cols(self, T, axis, adjoint=False):
+        if self.diag.size == 1:
+            return O.scale(T, float(self.diag[0]))
+        d = self._d(T.dtype)
+        return T * (d[:, None] if axis == 0 else d[None, :])
+
     def __call__(self, x):
         if self.shape[1] == 1 and not O.is_array(x):
             return float(self.diag[0]) * x
@@ -136,6 +163,9 @@ class IdentityOperator(DiagonalOperator):
     def _adj(self, t):
         return t
 
+    def _apply_cols(self, T, axis, adjoint=False):
+        return T
+
 
 class NullOperator(LinearOperator):
     """``base.py:601-622``."""
@@ -150,6 +180,11 @@ class NullOperator(LinearOperator):
 
     def _adj(self, t):
         return torch.zeros(self.shape[1], dtype=t.dtype, device=t.device)
+
+    def _apply_cols(self, T, axis, adjoint=False):
+        n = self.shape[1] if adjoint else self.shape[0]
+        shape = (n, T.shape[1]) if axis == 0 else (T.shape[0], n)
+        return torch.zeros(shape, dtype=T.dtype, device=T.device)
 
     def eigenvals(self, k, which='LM', **kwargs):
         return np.zeros(shape=(k,), dtype=self.dtype)
@@ -256,3 +291,250 @@ class PolynomialLinearOperator(LinearOperator):
         if self.is_symmetric:
             return self._apply(t)
         return self._poly(t, self.Linop._adj)
+
+    def _apply_cols(self, T, axis, adjoint=False):
+        adjoint = adjoint and not self.is_symmetric
+        return self._poly(T, lambda Z: self.Linop._apply_cols(Z, axis, adjoint))
+
+
+class KroneckerProduct(LinearOperator):
+    r"""Kronecker product of ``linop1`` = A (k x l) and ``linop2`` = B (n x m) (``base.py:715-803``):
+    ``K x = vec(B X A^T)`` with ``X = x.reshape(m, l)`` and ``K^* y = vec(B^* Y A)`` with ``Y = y.reshape(n, k)``
+    (C order), i.e. the matrix ``np.kron(B, A)``, of shape ``(n k, m l)``.  Both factors act through
+    ``_apply_cols``: one ``torch.matmul`` / ``pcs_csr_spmm`` / stencil launch per factor where it has a batched
+    form.  ``lipschitz_cst`` is the product of the factors' constants (``inf`` until they have one);
+    ``compute_lipschitz_cst`` computes the missing ones and multiplies: ``||A (x) B|| = ||A|| ||B||`` exactly."""
+
+    def __init__(self, linop1, linop2):
+        self.linop1, self.linop2 = linop1, linop2
+        super().__init__(shape=(linop2.shape[0] * linop1.shape[0], linop2.shape[1] * linop1.shape[1]),
+                         dtype=linop1.dtype, lipschitz_cst=_lip_product(linop1, linop2))
+
+    def _apply_cols(self, T, axis, adjoint=False):
+        A, B = self.linop1, self.linop2
+        (k, l), (n, m) = (A.shape, B.shape) if not adjoint else (A.shape[::-1], B.shape[::-1])
+        if axis == 1:
+            nb = T.shape[0]
+            Z = A._apply_cols(T.reshape(nb * m, l), 1, adjoint)
+            return B._apply_mid(Z.reshape(nb, m, k), adjoint).reshape(nb, n * k)
+        nb = T.shape[1]
+        Z = B._apply_cols(T.reshape(m, l * nb), 0, adjoint)
+        return A._apply_mid(Z.reshape(n, l, nb), adjoint).reshape(n * k, nb)
+
+    def _apply(self, t):
+        return self._apply_cols(t.reshape(1, -1), 1).reshape(-1)
+
+    def _adj(self, t):
+        return self._apply_cols(t.reshape(1, -1), 1, adjoint=True).reshape(-1)
+
+    def compute_lipschitz_cst(self, **kwargs):
+        for op in (self.linop1, self.linop2):
+            if op.lipschitz_cst == np.inf:
+                op.compute_lipschitz_cst(**kwargs)
+        self.lipschitz_cst = self.diff_lipschitz_cst = float(self.linop1.lipschitz_cst * self.linop2.lipschitz_cst)
+
+
+def _lip_product(op1, op2):
+    a, b = op1.lipschitz_cst, op2.lipschitz_cst
+    return np.inf if np.inf in (a, b) else a * b
+
+
+class KroneckerSum(LinearOperator):
+    r"""Kronecker sum of two square operators ``linop1`` = A (l x l) and ``linop2`` = B (m x m)
+    (``base.py:806-886``): ``S x = vec(X A^T + B X)`` with ``X = x.reshape(m, l)``, the matrix
+    ``kron(I_m, A) + kron(B, I_l)``.  The reference does not check the shapes; anything but two square factors is
+    a ``ValueError`` here.  The second term is accumulated into the first where the factor can
+    (``pcs_csr_spmm`` with ``accumulate``, ``torch.addmm``).  ``lipschitz_cst`` starts as the sum of the factors'
+    constants, as in the reference; ``compute_lipschitz_cst`` is the inherited device Lanczos."""
+
+    def __init__(self, linop1, linop2):
+        if linop1.shape[0] != linop1.shape[1] or linop2.shape[0] != linop2.shape[1]:
+            raise ValueError('KroneckerSum is defined for two square operators.')
+        self.linop1, self.linop2 = linop1, linop2
+        super().__init__(shape=(linop2.shape[0] * linop1.shape[0], linop2.shape[1] * linop1.shape[1]),
+                         dtype=linop1.dtype, lipschitz_cst=linop1.lipschitz_cst + linop2.lipschitz_cst)
+
+    def _apply_cols(self, T, axis, adjoint=False):
+        A, B = self.linop1, self.linop2
+        l, m = A.shape[0], B.shape[0]
+        if axis == 1:
+            nb = T.shape[0]
+            first = A._apply_cols(T.reshape(nb * m, l), 1, adjoint)
+            if nb == 1:
+                return B._apply_cols_acc(T.reshape(m, l), 0, adjoint, first).reshape(1, m * l)
+            return O.add(first.reshape(nb, m * l), B._apply_mid(T.reshape(nb, m, l), adjoint).reshape(nb, m * l))
+        nb = T.shape[1]
+        first = B._apply_cols(T.reshape(m, l * nb), 0, adjoint)
+        return O.add(first.reshape(m * l, nb), A._apply_mid(T.reshape(m, l, nb), adjoint).reshape(m * l, nb))
+
+    def _apply(self, t):
+        return self._apply_cols(t.reshape(1, -1), 1).reshape(-1)
+
+    def _adj(self, t):
+        return self._apply_cols(t.reshape(1, -1), 1, adjoint=True).reshape(-1)
+
+
+def khatri_rao_csr(A, B):
+    """The Khatri-Rao matrix of two SciPy sparse factors A (k x l) and B (n x l) as CSR with sorted indices:
+    column c is ``kron(B[:, c], A[:, c])`` (row ``j k + i`` holds ``B[j, c] A[i, c]``), ``nnz(A_c) nnz(B_c)``
+    entries, assembled on the host without the dense matrix."""
+    A, B = sparse.csc_matrix(A), sparse.csc_matrix(B)
+    (k, l), n = A.shape, B.shape[0]
+    if B.shape[1] != l:
+        raise ValueError('Invalid shapes.')
+    na, nb = np.diff(A.indptr).astype(np.int64), np.diff(B.indptr).astype(np.int64)
+    per_col = na * nb
+    total = int(per_col.sum())
+    col = np.repeat(np.arange(l, dtype=np.int64), per_col)
+    within = np.arange(total, dtype=np.int64) - np.repeat(np.cumsum(per_col) - per_col, per_col)
+    # entry (q, p) of column c pairs the q-th entry of B_c with the p-th entry of A_c
+    q, p = within // np.maximum(na[col], 1), within % np.maximum(na[col], 1)
+    ia, ib = A.indptr[col] + p, B.indptr[col] + q
+    rows = B.indices[ib].astype(np.int64) * k + A.indices[ia]
+    data = np.asarray(B.data)[ib] * np.asarray(A.data)[ia]
+    M = sparse.coo_matrix((data, (rows, col)), shape=(n * k, l)).tocsr()
+    M.sort_indices()
+    return M
+
+
+class KhatriRaoProduct(LinearOperator):
+    r"""Khatri-Rao (column-wise Kronecker) product of ``linop1`` = A (k x l) and ``linop2`` = B (n x l)
+    (``base.py:889-989``): column ``c`` of the matrix is ``np.kron(B[:, c], A[:, c])``; ``K x = vec(B diag(x) A^T)``
+    and ``K^* y = diag(B^* Y A)`` with ``Y = y.reshape(n, k)``; shape ``(n k, l)``.
+
+    Output shapes are the reference's: with two dense factors ``__call__`` returns the **2-D** array
+    ``(B * x) A^T`` of shape ``(n, k)``; every other pair returns the flat ``(n k,)`` vector; ``adjoint`` returns
+    ``(l,)``.  With two sparse factors the reference's branch is broken under current SciPy (forward: a 0-d object
+    array, adjoint: shape ``(1, l)``); that pair returns the values and shapes of the dense branch here (forward
+    ``(n, k)``, adjoint ``(l,)``).
+
+    Routes: a dense pair runs the fused kernels ``pcs_khatri_rao_fwd`` / ``pcs_khatri_rao_adj`` while
+    ``k n <= KR_MAX_NK`` and ``k + n <= KR_MAX_ROWS`` (the LDS and register budget derived in
+    ``csrc/khatri_rao.hip``) and, for the adjoint, inside the measured boundary of ``_ops.kr_route``; the ``torch``
+    composition ``mm(B * x, A^T)`` / ``sum(mm(Y, A) * B, 0)`` beyond; a
+    sparse pair assembles the Khatri-Rao matrix itself as CSR once on the host (``khatri_rao_csr``) and applies it
+    and its transpose with ``pcs_csr_spmv``; any other pair takes the reference's route through ``diag(x)`` and the
+    diagonal of ``B^* Y A``, on the device via ``_apply_cols``."""
+
+    def __init__(self, linop1, linop2):
+        if linop1.shape[1] != linop2.shape[1]:
+            raise ValueError('Invalid shapes.')
+        self.linop1, self.linop2 = linop1, linop2
+        super().__init__(shape=(linop2.shape[0] * linop1.shape[0], linop2.shape[1]), dtype=linop1.dtype,
+                         lipschitz_cst=_lip_product(linop1, linop2))
+        both = isinstance(linop1, ExplicitLinearOperator) and isinstance(linop2, ExplicitLinearOperator)
+        self._dense_pair = both and linop1.is_dense and linop2.is_dense
+        self._sparse_pair = both and linop1.is_sparse and linop2.is_sparse
+        self._csr, self._ws = {}, {}
+        self._host = {}
+
+    def _route(self, dtype=torch.float64, adjoint=False):
+        """'fused', 'torch', 'csr' or 'generic'."""
+        if self._dense_pair:
+            return O.kr_route(self.linop1.shape[0], self.linop2.shape[0], dtype, adjoint)
+        return 'csr' if self._sparse_pair else 'generic'
+
+    def _matrix(self, dtype, transposed):
+        A = self._csr.get((dtype, transposed))
+        if A is None:
+            h = self._host.get(False)
+            if h is None:
+                h = self._host[False] = khatri_rao_csr(self.linop1.mat, self.linop2.mat)
+            if transposed:
+                h = self._host.get(True)
+                if h is None:
+                    h = self._host[False].T.tocsr()
+                    h.sort_indices()
+                    self._host[True] = h
+            A = self._csr[(dtype, transposed)] = O.DeviceCSR(h, dtype)
+        return A
+
+    def _workspace(self, dtype):
+        ws = self._ws.get(dtype)
+        if ws is None:
+            need = O.kr_fwd_plan(self.linop1.shape[0], self.linop2.shape[0], self.shape[1])[2]
+            ws = self._ws[dtype] = torch.empty(need, dtype=torch.float64, device=O.device())
+        return ws
+
+    def _apply(self, t):
+        A, B, route = self.linop1, self.linop2, self._route(t.dtype)
+        if route == 'fused':
+            return O.khatri_rao_fwd(A._m(t.dtype), B._m(t.dtype), t, self._workspace(t.dtype)).reshape(-1)
+        if route == 'torch':
+            return torch.mm(B._m(t.dtype) * t[None, :], A._m(t.dtype).T).reshape(-1)
+        if route == 'csr':
+            return O.spmv(self._matrix(t.dtype, False), t)
+        Z = A._apply_cols(torch.diag(t), 0)                       # (k, l): A diag(x)
+        return B._apply_cols(Z.T.contiguous(), 0).reshape(-1)     # (n, k): B diag(x) A^T
+
+    def _adj(self, t):
+        A, B, route = self.linop1, self.linop2, self._route(t.dtype, adjoint=True)
+        k, n = A.shape[0], B.shape[0]
+        if route == 'fused':
+            return O.khatri_rao_adj(A._m(t.dtype), B._m(t.dtype), t.contiguous())
+        if route == 'torch':
+            return torch.sum(torch.mm(t.reshape(n, k), A._m(t.dtype)) * B._m(t.dtype), dim=0)
+        if route == 'csr':
+            return O.spmv(self._matrix(t.dtype, True), t)
+        Z = A._apply_cols(t.reshape(n, k), 1, adjoint=True)       # (n, l): Y A
+        return torch.diagonal(B._apply_cols(Z, 0, adjoint=True)).contiguous()   # diag(B^* Y A)
+
+    def _apply_cols(self, T, axis, adjoint=False):
+        if self._sparse_pair:                # the assembled CSR matrix: one batched product
+            return O.spmm(self._matrix(T.dtype, adjoint), T, axis)
+        return LinearOperator._apply_cols(self, T, axis, adjoint)
+
+    def __call__(self, x):
+        out = LinearOperator.__call__(self, x)
+        if self._dense_pair or self._sparse_pair:
+            return out.reshape(self.linop2.shape[0], self.linop1.shape[0])
+        return out
+
+
+def BlockOperator(linops, n_jobs=1):
+    """``base.py:339-450``: the operator of a rectangular layout of blocks ``[[A, B], [C, D]]``, a vertical stack
+    of horizontal stacks.  ``n_jobs`` is accepted and ignored.  All rows must have equal length and blocks of
+    compatible shapes, else ``ValueError``."""
+    rows = [list(r) for r in linops]
+    if not rows or not rows[0] or len({len(r) for r in rows}) != 1:
+        raise ValueError('BlockOperator: every row of blocks must have the same, non-zero length.')
+    for r in rows:
+        if len({op.shape[0] for op in r}) != 1:
+            raise ValueError('BlockOperator: the blocks of a row must have equal numbers of rows.')
+    for col in zip(*rows):
+        if len({op.shape[1] for op in col}) != 1:
+            raise ValueError('BlockOperator: the blocks of a column must have equal numbers of columns.')
+    return LinOpVStack(*[LinOpHStack(*r) for r in rows])
+
+
+class BlockDiagonalOperator(LinearOperator):
+    """``base.py:453-548``: ``diag(L_1, ..., L_k)``: each operator acts on its own slice of the input and the
+    results are concatenated.  ``n_jobs`` is accepted and ignored.  ``lipschitz_cst`` is the maximum of the
+    blocks' constants (``inf`` until every block has one)."""
+
+    def __init__(self, *linops, n_jobs=1):
+        if not linops:
+            raise ValueError('BlockDiagonalOperator needs at least one operator.')
+        self.linops, self.n_jobs = list(linops), n_jobs
+        self._rows = _sections([op.shape[0] for op in linops])
+        self._cols = _sections([op.shape[1] for op in linops])
+        dts = {op.dtype for op in linops}
+        super().__init__(shape=(self._rows[-1], self._cols[-1]), dtype=dts.pop() if len(dts) == 1 else None,
+                         is_symmetric=all(op.is_symmetric for op in linops),
+                         lipschitz_cst=max(op.lipschitz_cst for op in linops))
+
+    def _apply(self, t):
+        from ..core.map import _cat
+        o = self._cols
+        return _cat([op._apply(t[o[i]:o[i + 1]]) for i, op in enumerate(self.linops)], t)
+
+    def _adj(self, t):
+        from ..core.map import _cat
+        o = self._rows
+        return _cat([op._adj(t[o[i]:o[i + 1]]) for i, op in enumerate(self.linops)], t)
+
+    def compute_lipschitz_cst(self, **kwargs):
+        for op in self.linops:
+            if op.lipschitz_cst == np.inf:
+                op.compute_lipschitz_cst(**kwargs)
+        self.lipschitz_cst = self.diff_lipschitz_cst = float(max(op.lipschitz_cst for op in self.linops))

@@ -153,6 +153,13 @@ class Convolve1DOp(LinearOperator):
     def _adj(self, t):
         return O.conv1d(t, self.dims, self.axis, self._hf.get(t.dtype), self.k, self.k - 1 - self.off)
 
+    def _apply_cols(self, T, axis, adjoint=False):
+        if len(self.dims) != 1:
+            return LinearOperator._apply_cols(self, T, axis, adjoint)
+        if adjoint:
+            return O.conv1d(T, tuple(T.shape), axis, self._hf.get(T.dtype), self.k, self.k - 1 - self.off)
+        return O.conv1d(T, tuple(T.shape), axis, self._h.get(T.dtype), self.k, self.off)
+
     def norm2(self):
         """||Conv1D||^2 exactly: the 1-D banded Gram matrix along the axis (linop/_spectral.py)."""
         return S.conv1d_norm2(self.dims[self.axis], self.filter, self.off)

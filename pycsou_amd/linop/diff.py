@@ -58,6 +58,11 @@ class FirstDerivativeOp(_DiffOp):
     def _adj(self, t):
         return O.deriv1(t, self.dims, self.axis, self.step, self.kind, self.edge, adjoint=True)
 
+    def _apply_cols(self, T, axis, adjoint=False):
+        if len(self.dims) != 1:
+            return LinearOperator._apply_cols(self, T, axis, adjoint)
+        return O.deriv1(T, tuple(T.shape), axis, self.step, self.kind, self.edge, adjoint=adjoint)
+
     def compute_lipschitz_cst(self, **kwargs):
         """Exact ||D|| = sqrt(lambda_max(D_1^T D_1)) of the 1-D stencil along the axis (K = I (x) D_1 (x) I;
         linop/_spectral.py), in place of the reference's ARPACK svds (pycsou/core/linop.py:279-321)."""
@@ -143,6 +148,11 @@ class SecondDerivativeOp(_DiffOp):
 
     def _adj(self, t):
         return O.deriv2(t, self.dims, self.axis, self.step, self.edge, adjoint=True)
+
+    def _apply_cols(self, T, axis, adjoint=False):
+        if len(self.dims) != 1:
+            return LinearOperator._apply_cols(self, T, axis, adjoint)
+        return O.deriv2(T, tuple(T.shape), axis, self.step, self.edge, adjoint=adjoint)
 
     def compute_lipschitz_cst(self, **kwargs):
         """Exact ||D2|| of the 1-D second-difference stencil along the axis (linop/_spectral.py)."""
