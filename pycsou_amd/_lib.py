@@ -307,6 +307,11 @@ def dbls(vals):
     return (ctypes.c_double * len(vals))(*[float(v) for v in vals])
 
 
+def dtype_code(dtype):
+    """PCS_F32 / PCS_F64 of a torch dtype (the engines run in one of the two)."""
+    return PCS_F32 if dtype == torch.float32 else PCS_F64
+
+
 def dtcode(t):
     if t.dtype == torch.float32:
         return PCS_F32

@@ -32,32 +32,15 @@ from ..func.penalty import L1Norm, L21Norm, SquaredL2Norm
 from ..linop.base import HomothetyMap
 from ..linop.conv import Convolve2DOp
 from ..linop.diff import GradientOp, LaplacianOp
+from ._loop import LaunchTimer, LoopControl
 
 # images at least this large launch chunks from C instead of replaying a captured graph
 NATIVE_MIN_PIXELS = int(os.environ.get('PCS_NATIVE_MIN_PIXELS', 1 << 20))
-
-
-HIST_CHUNK = 4096  # iterations of device history allocated at first; doubled as the loop goes on
 
 # deferred finalization (pcs_pds2d_args.fin_partials, csrc/pds_ctrl.hpp): each step launch finalizes the
 # previous launch's partials in a workgroup of its own instead of reducing its own at its end.
 # PCS_DEFER_FIN=0: diagnostics, the in-launch reduction.
 DEFER_FIN = os.environ.get('PCS_DEFER_FIN', '1') != '0'
-
-
-def grow_hist(hist, ctrl, need_iters, total):
-    """Device history with room for `need_iters` iterations (at most `total`): `hist` itself, or a
-    copy twice as long with the loop control's length updated (stream-ordered after every
-    iteration already enqueued).  A max_iter of 1e9 with accuracy_threshold doing the stopping
-    must not allocate 2 * max_iter doubles up front."""
-    have = (hist.numel() - 2) // 2
-    if need_iters + 1 <= have or have >= total:
-        return hist
-    cap = min(total, max(2 * have, need_iters + 1))
-    new = torch.full((2 * cap + 2,), float('nan'), dtype=torch.float64, device=hist.device)
-    new[:hist.numel()].copy_(hist)
-    ctrl.view(torch.int32)[5].fill_(int(new.numel()))  # Ctrl.hist_len (csrc/pds_ctrl.hpp)
-    return new
 
 
 def _half_loss_data(F):
@@ -301,7 +284,7 @@ class APGD2DEngine:
         # Conv^T y formed once in fp64 (y = -shift exactly)
         self.cty = spec['conv']._adj(-O.to_dev(spec['shift'], torch.float64)).to(dtype).contiguous()
         a = L.Apgd2dArgs()
-        a.dtype = L.PCS_F32 if dtype == torch.float32 else L.PCS_F64
+        a.dtype = L.dtype_code(dtype)
         a.gkind, a.n0, a.n1, a.half = spec['gkind'], n0, n1, half
         a.taps0, a.taps1 = self.taps[0].data_ptr(), self.taps[1].data_ptr()
         a.tau, a.lam = float(tau), float(spec['lam'])
@@ -314,29 +297,23 @@ class APGD2DEngine:
             raise ValueError('problem not supported by the fused APGD step')
         self.nblocks = int(self.lib.pcs_apgd2d_nblocks(ctypes.byref(a)))
         self.partials = torch.empty(4 * self.nblocks, dtype=torch.float64, device=dev)
-        self.ctrl = torch.zeros(int(self.lib.pcs_ctrl_bytes()) // 8, dtype=torch.float64, device=dev)
+        self.ctl = LoopControl(dev)
         # the reduction counters start at 0 and every launch leaves them at 0
         self.ws = torch.zeros(int(self.lib.pcs_apgd2d_ws_bytes(ctypes.byref(a))) // 8 + 2, dtype=torch.float64,
                               device=dev)
         a.partials, a.ctrl, a.ws = self.partials.data_ptr(), self.ctrl.data_ptr(), self.ws.data_ptr()
-        self.hist = None
-        self.ctrl_host = torch.zeros(2, dtype=torch.int32).pin_memory()
+
+    ctrl = property(lambda self: self.ctl.ctrl)
+    hist = property(lambda self: self.ctl.hist)
 
     def coeffs(self, k0, n, t_old):
         return apgd_coeffs(self.acceleration, self.d, k0, n, t_old)
 
-    def start(self, max_iter, min_iter, thr, total=None):
+    def start(self, max_iter, min_iter, thr):
         """Iterate x0, past_aux 0, a fresh loop control and a history with room for the first chunks."""
-        total = max(int(min_iter), int(max_iter)) + 1 if total is None else total
-        hist_len = 2 * min(total, max(HIST_CHUNK, 2 * self.chunk)) + 2
-        if self.hist is None or self.hist.numel() < hist_len:
-            self.hist = torch.empty(hist_len, dtype=torch.float64, device=self.x0.device)
-        self.hist.fill_(float('nan'))
         self.X[0].copy_(self.x0)
         self.AUX[0].zero_()
-        L.check(self.lib.pcs_ctrl_init2(L.ptr(self.ctrl), int(min_iter), int(max_iter), float(thr), 0,
-                                        int(self.hist.numel()), L.stream()), 'pcs_ctrl_init2')
-        return total
+        return self.ctl.start(max_iter, min_iter, thr, False, chunk=self.chunk)
 
     def launch(self, coeffs):
         """len(coeffs) (even) iterations from buffer parity 0, launched back to back."""
@@ -348,49 +325,44 @@ class APGD2DEngine:
         """The reference loop from x0 (solver.py:55-76): (n, x, past_aux, past_t, hist[n])."""
         total = self.start(max_iter, min_iter, accuracy_threshold)
         n_chunks = -(-total // self.chunk)
-        t_old, pending = 1, []
+        t_old = 1
         for k in range(n_chunks):
-            self.hist = grow_hist(self.hist, self.ctrl, (k + 1) * self.chunk + 1, total)
+            self.ctl.reserve((k + 1) * self.chunk + 2)
             coeffs, t_old = self.coeffs(k * self.chunk, self.chunk, t_old)
             self.launch(coeffs)
-            ev = torch.cuda.Event()
-            self.ctrl_host.copy_(self.ctrl.view(torch.int32)[:2], non_blocking=True)
-            ev.record()
-            pending.append(ev)
-            if len(pending) >= 2:  # one chunk in flight behind the one whose control is read
-                pending.pop(0).synchronize()
-                if int(self.ctrl_host[1]) != 0:
-                    break
+            self.ctl.read_async()
+            if self.ctl.poll(lag=1) is not None:  # one chunk in flight behind the one whose control is read
+                break
         torch.cuda.synchronize()
-        n = int(self.ctrl.view(torch.int32)[:1].cpu()[0])
-        h = self.hist[:2 * n].cpu().numpy().reshape(n, 2)[:, 0].copy() if n > 0 else np.zeros((0,))
+        n = self.ctl.iterations()
+        h = self.ctl.rows(n)[:, 0].copy()
         past_t = self.coeffs(0, n, 1)[1]
         return n, self.X[n % 2], self.AUX[n % 2], past_t, h
+
+
+def _common_args(a, spec, dtype, tau, sigma, rho, with_k=True):
+    """The fields pcs_pds2d_args and pcs_pds2d_stencil_args share by name, from a spec and the step
+    sizes (`with_k`: K's kind, edge rule and weights, which only the general-stencil specs carry)."""
+    a.dtype = L.dtype_code(dtype)
+    a.hkind, a.gkind = spec['hkind'], spec['gkind']
+    a.n0, a.n1 = spec['shape']
+    a.tau, a.sigma, a.rho, a.lam = float(tau), float(sigma), float(rho), spec['lam']
+    a.step0, a.step1 = spec['steps']
+    a.seg_a, a.seg_b = spec['seg']
+    if with_k:
+        a.kkind, a.edge = spec['kkind'], int(spec['edge'])
+        a.w0, a.w1 = spec['weights']
+    if isinstance(a, L.PdsArgs):  # one slab, the whole image: no halos
+        a.row0, a.rows = 0, a.n0
+    return a
 
 
 class PDS2DEngine:
     """Device state + captured loop for one fused 2-D PDS problem."""
 
     def __init__(self, spec, dtype, tau, sigma, rho, x0, z0, chunk=32, use_graph=True):
-        self.lib = L.gpu()
-        self.spec = spec
-        self.dtype = dtype
-        n0, n1 = spec['shape']
-        self.N = n0 * n1
-        self.X = [x0.to(dtype).clone(), torch.empty(self.N, dtype=dtype, device=x0.device)]
-        self.Z = [z0.to(dtype).clone(), torch.empty(2 * self.N, dtype=dtype, device=x0.device)]
-        dev = self.X[0].device
-        self.chunk = max(2, chunk + (chunk % 2))
-        self.use_graph = use_graph
-        a = L.PdsArgs()
-        a.dtype = L.PCS_F32 if dtype == torch.float32 else L.PCS_F64
-        a.hkind, a.gkind = spec['hkind'], spec['gkind']
-        a.n0, a.n1, a.row0, a.rows = n0, n1, 0, n0
-        a.halo_x = a.halo_z = a.halo_y = 0
-        a.tau, a.sigma, a.rho, a.lam = float(tau), float(sigma), float(rho), spec['lam']
-        a.step0, a.step1 = spec['steps']
-        a.seg_a, a.seg_b = spec['seg']
-        self.keep = []
+        dev = self._init_state(spec, dtype, x0, z0, chunk, use_graph)
+        a = _common_args(L.PdsArgs(), spec, dtype, tau, sigma, rho, with_k=False)
         fk = spec['fkind']
         self.conv = None
         if fk in (L.PCS_F_DENOISE, L.PCS_F_SEPCONV):
@@ -399,7 +371,7 @@ class PDS2DEngine:
             a.y = self.y.data_ptr()
         if fk == L.PCS_F_SEPCONV:
             conv = spec['conv']
-            sep = conv.separable(rtol=2e-7 if dtype == torch.float32 else 1e-13)
+            sep = conv.separable(rtol=sep_rtol(dtype))
             if sep is not None:
                 t0, t1, half = sep
                 self.taps = [torch.as_tensor(t0).to(device=dev, dtype=dtype),
@@ -415,34 +387,57 @@ class PDS2DEngine:
                     a.cty, a.ntaps = self.cty.data_ptr(), self.ntaps.data_ptr()
             else:
                 fk = L.PCS_F_GRADBUF
-                self.conv = conv
-                # device PSF copies / packed correlation plans / the FFT plan exist before capture
-                conv._h.get(dtype), conv._hf.get(dtype)
-                self.plans = (conv.plan(dtype, False), conv.plan(dtype, True))
-                if self.plans[0] is None or self.plans[1] is None:
-                    conv.fft(dtype)
-                self.R = torch.empty(self.N, dtype=dtype, device=dev)
-                self.Gb = torch.empty(self.N, dtype=dtype, device=dev)
+                self._init_grad_conv(conv, dev)
                 a.gbuf = self.Gb.data_ptr()
         a.fkind = fk
-        self.fkind = fk
-        self.args = a
-        self.nblocks = int(self.lib.pcs_pds2d_nblocks(ctypes.byref(a)))
+        self._init_loop_state(a, fk, self.lib.pcs_pds2d_nblocks, self.lib.pcs_pds2d_ws_bytes, fk != L.PCS_F_GRADBUF)
+
+    # ---- the pieces of a constructor (the subclasses' differ in the arguments between them)
+    def _init_state(self, spec, dtype, x0, z0, chunk, use_graph, ncomp=2):
+        """The iterate ping-pong buffers (z of `ncomp` components) and the loop's shape; the device."""
+        self.lib = L.gpu()
+        self.spec = spec
+        self.dtype = dtype
+        n0, n1 = spec['shape']
+        self.N = n0 * n1
+        dev = x0.device
+        self.X = [x0.to(dtype).clone(), torch.empty(self.N, dtype=dtype, device=dev)]
+        self.Z = [z0.to(dtype).clone(), torch.empty(ncomp * self.N, dtype=dtype, device=dev)]
+        self.chunk = max(2, chunk + (chunk % 2))
+        self.use_graph = use_graph
+        return dev
+
+    def _init_grad_conv(self, conv, dev):
+        """GRADBUF: the device PSF copies / packed correlation plans / the FFT plan exist before any
+        capture; the residual and gradient buffers."""
+        self.conv = conv
+        conv._h.get(self.dtype), conv._hf.get(self.dtype)
+        self.plans = (conv.plan(self.dtype, False), conv.plan(self.dtype, True))
+        if self.plans[0] is None or self.plans[1] is None:
+            conv.fft(self.dtype)
+        self.R = torch.empty(self.N, dtype=self.dtype, device=dev)
+        self.Gb = torch.empty(self.N, dtype=self.dtype, device=dev)
+
+    def _init_loop_state(self, a, fk, nblocks_fn, ws_bytes_fn, may_run_native):
+        """The step arguments `a` are complete but for what the loop owns: partials, the loop control,
+        the reduction workspace (in-kernel reduce + finalize, one launch per iteration; its counters
+        must start at 0)."""
+        dev = self.X[0].device
+        self.args, self.fkind = a, fk
+        self.nblocks = int(nblocks_fn(ctypes.byref(a)))
         self._alloc_partials(a, dev)
-        self.ctrl = torch.zeros(int(self.lib.pcs_ctrl_bytes()) // 8, dtype=torch.float64, device=dev)
+        self.ctl = LoopControl(dev)
         a.ctrl = self.ctrl.data_ptr()
-        # in-kernel reduce + finalize (one launch per iteration); counters must start at 0
-        self.fused_finalize = True
-        self.ws = torch.zeros(int(self.lib.pcs_pds2d_ws_bytes(ctypes.byref(a))) // 8 + 2, dtype=torch.float64,
-                              device=dev)
+        self.ws = torch.zeros(int(ws_bytes_fn(ctypes.byref(a))) // 8 + 2, dtype=torch.float64, device=dev)
         a.ws = self.ws.data_ptr()
         self.graph = None
-        self.hist = None
-        self.ctrl_host = torch.zeros(2, dtype=torch.int32).pin_memory()
         # large images: each chunk is launched back to back from C (pcs_pds2d_run) -- per-launch
         # host cost is far below the step, and back-to-back launches measured faster than
         # replaying a captured graph of the same launches; small images keep the graph
-        self.native = fk != L.PCS_F_GRADBUF and self.N >= NATIVE_MIN_PIXELS
+        self.native = may_run_native and self.N >= NATIVE_MIN_PIXELS
+
+    ctrl = property(lambda self: self.ctl.ctrl)
+    hist = property(lambda self: self.ctl.hist)
 
     def _alloc_partials(self, a, dev):
         """[nblocks][4] partials; with deferred finalization two such arrays, swapped with the
@@ -491,32 +486,32 @@ class PDS2DEngine:
 
     # one iteration with parity p (reads buffers p, writes 1-p)
     def _iteration(self, p, hist):
-        a, lib, st = self.args, self.lib, L.stream()
+        a, st = self.args, L.stream()
         if self.fkind == L.PCS_F_GRADBUF:
             self._grad_conv(p, st)
         self._bind(a, p)
-        a.hist = hist.data_ptr() if self.fused_finalize else None
+        a.hist = hist.data_ptr()
         self._step_call(st)
-        if not self.fused_finalize:
-            L.check(lib.pcs_pds_reduce_finalize(L.ptr(self.partials), self.nblocks, L.ptr(self.ctrl), L.ptr(hist),
-                                                st), 'pcs_pds_reduce_finalize')
 
-    def _grad_conv(self, p, st):
+    def _grad_conv(self, p, st, around=lambda name, launch: launch()):
         """GRADBUF: r = h*x - y (residual fused into the forward pass), g = h^T r -- the
-        packed-plan correlation kernel (pcs_conv2d_planned) when the PSF fits its tiers."""
+        packed-plan correlation kernel (pcs_conv2d_planned) when the PSF fits its tiers.  Each of the
+        two launches runs as around(name, launch) (the kernel timers put their events there)."""
         c, a, lib = self.conv, self.args, self.lib
         fwd, adj = self.plans
         n0, n1 = c.dims
         if fwd is not None and adj is not None:
-            L.check(lib.pcs_conv2d_planned(a.dtype, L.ptr(self.X[p]), L.ptr(self.R), n0, n1, L.ptr(fwd[1]), fwd[0],
-                                           L.ptr(self.y), -1.0, st), 'pcs_conv2d_planned')
-            L.check(lib.pcs_conv2d_planned(a.dtype, L.ptr(self.R), L.ptr(self.Gb), n0, n1, L.ptr(adj[1]), adj[0],
-                                           None, 0.0, st), 'pcs_conv2d_planned')
+            around('conv_fwd', lambda: L.check(lib.pcs_conv2d_planned(
+                a.dtype, L.ptr(self.X[p]), L.ptr(self.R), n0, n1, L.ptr(fwd[1]), fwd[0], L.ptr(self.y), -1.0, st),
+                'pcs_conv2d_planned'))
+            around('conv_adj', lambda: L.check(lib.pcs_conv2d_planned(
+                a.dtype, L.ptr(self.R), L.ptr(self.Gb), n0, n1, L.ptr(adj[1]), adj[0], None, 0.0, st),
+                'pcs_conv2d_planned'))
             return
         # wider PSFs: the FFT-domain plan (rocFFT; cost independent of the PSF size)
         f = c.fft(self.dtype)
-        f.apply(self.X[p], b=self.y, beta=-1.0, out=self.R)
-        f.apply(self.R, adjoint=True, out=self.Gb)
+        around('conv_fwd', lambda: f.apply(self.X[p], b=self.y, beta=-1.0, out=self.R))
+        around('conv_adj', lambda: f.apply(self.R, adjoint=True, out=self.Gb))
 
     def _chunk(self, hist):
         for i in range(self.chunk):
@@ -528,22 +523,25 @@ class PDS2DEngine:
         a.hist = hist.data_ptr()
         self._run_call(self.chunk)
 
+    def _capture(self):
+        """One chunk on the current history captured into self.graph (the history is captured by
+        pointer: whoever replaces it drops the graph)."""
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._chunk(self.hist)
+        self.graph = g
+
     # ---- fixed-count loop for benchmarking (bench.py): no early stop, optional per-step events
     def prepare_fixed(self, total_iters, chunk):
         """Device state for `total_iters` iterations that never stop early, captured in
         graphs of `chunk` (even) iterations."""
         self.chunk = chunk
         self._fixed_p = 0
-        hist_len = 2 * (total_iters + 1) + 2
-        self.hist = torch.empty(hist_len, dtype=torch.float64, device=self.X[0].device)
-        L.check(self.lib.pcs_ctrl_init2(L.ptr(self.ctrl), int(total_iters), int(total_iters), -1.0, 1, hist_len,
-                                        L.stream()), 'pcs_ctrl_init2')
-        torch.cuda.synchronize()
+        self.ctl.start_fixed(total_iters, total_iters + 1)
         if not self.native:
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self._chunk(self.hist)
-            torch.cuda.synchronize()
+            self._capture()
+        torch.cuda.synchronize()
 
     def replay(self):
         if self.native:
@@ -574,123 +572,70 @@ class PDS2DEngine:
         self._fixed_p = p
         self._flush(p, self.hist)
 
+    def _start_timed(self, n):
+        """Fresh loop state that runs all of n eager launches on the history as it is (the in-kernel
+        reduce + finalize is timed too); n, cut to what the history holds."""
+        n = min(n, (self.hist.numel() - 2) // 2 - 1)
+        self.ctl.start_fixed(n + 1)
+        return n
+
     def time_iteration_kernels(self, n):
         """Median duration (ms) of each kernel of an iteration over n eager iterations, HIP
         events on the launching stream around every launch: {'step': ...} and, for a
         non-separable PSF, {'conv_fwd': ..., 'conv_adj': ...}.  (Median: a single launch
         delayed by an unrelated host or driver event does not move it.)"""
-        a, lib = self.args, self.lib
-        st = torch.cuda.current_stream()
-        n = min(n, (self.hist.numel() - 2) // 2 - 1)
-        L.check(lib.pcs_ctrl_init2(L.ptr(self.ctrl), n + 1, n + 1, -1.0, 1, int(self.hist.numel()), L.stream()),
-                'pcs_ctrl_init2')
-        names = ['conv_fwd', 'conv_adj', 'step'] if self.fkind == L.PCS_F_GRADBUF else ['step']
-        ev = {k: [] for k in names}
-
-        def timed(name, fn):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(st)
-            fn()
-            e1.record(st)
-            ev[name].append((e0, e1))
+        a = self.args
+        n = self._start_timed(n)
+        timed = LaunchTimer()
         for i in range(n):
             p = i % 2
-            if self.fkind == L.PCS_F_GRADBUF and (self.plans[0] is None or self.plans[1] is None):
-                # PSF wider than the direct tiers: the FFT-domain plan's two passes
-                f = self.conv.fft(self.dtype)
-                timed('conv_fwd', lambda: f.apply(self.X[p], b=self.y, beta=-1.0, out=self.R))
-                timed('conv_adj', lambda: f.apply(self.R, adjoint=True, out=self.Gb))
-            elif self.fkind == L.PCS_F_GRADBUF:
-                fwd, adj = self.plans
-                n0, n1 = self.conv.dims
-                timed('conv_fwd', lambda: L.check(lib.pcs_conv2d_planned(
-                    a.dtype, L.ptr(self.X[p]), L.ptr(self.R), n0, n1, L.ptr(fwd[1]), fwd[0], L.ptr(self.y), -1.0,
-                    L.stream()), 'pcs_conv2d_planned'))
-                timed('conv_adj', lambda: L.check(lib.pcs_conv2d_planned(
-                    a.dtype, L.ptr(self.R), L.ptr(self.Gb), n0, n1, L.ptr(adj[1]), adj[0], None, 0.0, L.stream()),
-                    'pcs_conv2d_planned'))
+            if self.fkind == L.PCS_F_GRADBUF:
+                self._grad_conv(p, L.stream(), timed)
             self._bind(a, p)
             a.hist = self.hist.data_ptr()
             timed('step', lambda: self._step_call(L.stream()))
         self._flush(n % 2, self.hist)
-        torch.cuda.synchronize()
-        return {k: float(np.median([s.elapsed_time(e) for s, e in v])) for k, v in ev.items()}
+        return timed.result(np.median)
 
     def time_step_kernel(self, n, stream=None):
         """Average duration (ms) of the fused step kernel over `n` eager launches, measured
         with HIP events on the stream the kernel runs on."""
         a = self.args
-        st = torch.cuda.current_stream() if stream is None else stream
-        # fresh loop state that runs all n launches (the in-kernel reduce + finalize is timed too)
-        n = min(n, (self.hist.numel() - 2) // 2 - 1)
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
-        L.check(self.lib.pcs_ctrl_init2(L.ptr(self.ctrl), n + 1, n + 1, -1.0, 1, int(self.hist.numel()), L.stream()),
-                'pcs_ctrl_init2')
-        ctrl, hist = a.ctrl, a.hist
+        n = self._start_timed(n)
+        timed = LaunchTimer(stream)
         a.hist = self.hist.data_ptr()
-        if not self.fused_finalize:
-            a.hist = None
         for i in range(n):
-            p = i % 2
-            self._bind(a, p)
-            evs[i][0].record(st)
-            self._step_call(L.stream())
-            evs[i][1].record(st)
+            self._bind(a, i % 2)
+            timed('step', lambda: self._step_call(L.stream()))
         self._flush(n % 2, self.hist)
-        torch.cuda.synchronize()
-        a.ctrl, a.hist = ctrl, hist
-        return float(np.mean([s.elapsed_time(e) for s, e in evs]))
+        return timed.result()['step']
 
     def run(self, max_iter, min_iter, accuracy_threshold, has_dual=True):
-        max_iter, min_iter = int(max_iter), int(min_iter)
-        total = max(min_iter, max_iter) + 1
-        hist_len = 2 * min(total, max(HIST_CHUNK, 2 * self.chunk)) + 2
-        if self.hist is None or self.hist.numel() < hist_len:
-            # the history buffer is captured by pointer: (re)capture when it grows
-            self.hist = torch.empty(hist_len, dtype=torch.float64, device=self.X[0].device)
+        ctl = self.ctl
+        total = ctl.start(max_iter, min_iter, accuracy_threshold, has_dual, chunk=self.chunk)
+        if ctl.replaced:
             self.graph = None
-        self.hist.fill_(float('nan'))
-        L.check(self.lib.pcs_ctrl_init2(L.ptr(self.ctrl), min_iter, max_iter, float(accuracy_threshold),
-                                        int(has_dual), int(self.hist.numel()), L.stream()), 'pcs_ctrl_init2')
-        n_chunks = -(-total // self.chunk)
-        if self.use_graph or self.native:
-            pending = []
-            for k in range(n_chunks):
-                grown = grow_hist(self.hist, self.ctrl, (k + 1) * self.chunk + 1, total)
-                if grown is not self.hist:
-                    self.hist, self.graph = grown, None
-                hist = self.hist
-                if self.graph is None and not self.native:
-                    torch.cuda.synchronize()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        self._chunk(hist)
-                    self.graph = g
-                if self.native:
-                    self._chunk_native(hist)
-                else:
-                    self.graph.replay()
-                ev = torch.cuda.Event()
-                self.ctrl_host.copy_(self.ctrl.view(torch.int32)[:2], non_blocking=True)
-                ev.record()
-                pending.append(ev)
-                if len(pending) >= 2:
-                    pending.pop(0).synchronize()
-                    if int(self.ctrl_host[1]) != 0:
-                        break
-        else:
-            for k in range(n_chunks):
-                self.hist = grow_hist(self.hist, self.ctrl, (k + 1) * self.chunk + 1, total)
+        for k in range(-(-total // self.chunk)):
+            if ctl.reserve((k + 1) * self.chunk + 2):
+                self.graph = None
+            if self.native:
+                self._chunk_native(self.hist)
+            elif self.use_graph:
+                if self.graph is None:
+                    self._capture()
+                self.graph.replay()
+            else:
                 self._chunk(self.hist)
-                if int(self.ctrl.view(torch.int32)[1].item()) != 0:
+                if ctl.stopped():
                     break
-        hist = self.hist
-        self._flush(0, hist, run=self.native)  # every chunk is an even number of launches
+                continue
+            ctl.read_async()
+            if ctl.poll(lag=1) is not None:  # one chunk in flight behind the one whose control is read
+                break
+        self._flush(0, self.hist, run=self.native)  # every chunk is an even number of launches
         torch.cuda.synchronize()
-        c = self.ctrl.view(torch.int32)[:2].cpu().numpy()
-        n = int(c[0])
-        h = hist[:2 * n].cpu().numpy().reshape(n, 2) if n > 0 else np.zeros((0, 2))
-        return n, self.X[n % 2], self.Z[n % 2], h
+        n = ctl.iterations()
+        return n, self.X[n % 2], self.Z[n % 2], ctl.rows(n)
 
 
 class PDS2DStencilEngine(PDS2DEngine):
@@ -699,31 +644,14 @@ class PDS2DStencilEngine(PDS2DEngine):
     hipGraph replay otherwise, GRADBUF convolutions before the step), another step kernel."""
 
     def __init__(self, spec, dtype, tau, sigma, rho, x0, z0, chunk=32, use_graph=True):
-        self.lib = L.gpu()
-        self.spec = spec
-        self.dtype = dtype
-        n0, n1 = spec['shape']
-        self.N = N = n0 * n1
-        nc = spec['ncomp']
-        dev = x0.device
-        self.X = [x0.to(dtype).clone(), torch.empty(N, dtype=dtype, device=dev)]
-        self.Z = [z0.to(dtype).clone(), torch.empty(nc * N, dtype=dtype, device=dev)]
-        self.chunk = max(2, chunk + (chunk % 2))
-        self.use_graph = use_graph
+        dev = self._init_state(spec, dtype, x0, z0, chunk, use_graph, spec['ncomp'])
         fk = spec['fkind']
         self.conv = None
         if fk in (L.PCS_F_DENOISE, L.PCS_F_GRADBUF):
             self.y = -O.to_dev(spec['shift'], dtype)  # y = -shift exactly
         if fk == L.PCS_F_GRADBUF:
-            conv = self.conv = spec['conv']
-            conv._h.get(dtype), conv._hf.get(dtype)
-            self.plans = (conv.plan(dtype, False), conv.plan(dtype, True))
-            if self.plans[0] is None or self.plans[1] is None:
-                conv.fft(dtype)  # created before any capture
-            self.R = torch.empty(N, dtype=dtype, device=dev)
-            self.Gb = torch.empty(N, dtype=dtype, device=dev)
+            self._init_grad_conv(spec['conv'], dev)
         gsrc = None if fk == L.PCS_F_NULL else (self.Gb if fk == L.PCS_F_GRADBUF else self.y)
-        self.fkind = fk
         # images the general-stencil row-marching kernel covers (pds_smarch.hpp: 64-column strips,
         # 4-column groups; fp32 and fp64, every K kind in fp64) run through pcs_pds2d_step with K in
         # the args; the rest through the tile kernel (pcs_pds2d_stencil_step).  PCS_STENCIL_MARCH=0:
@@ -732,16 +660,9 @@ class PDS2DStencilEngine(PDS2DEngine):
         a = None
         f64 = dtype == torch.float64
         if dtype in (torch.float32, torch.float64) and os.environ.get('PCS_STENCIL_MARCH', '1') != '0':
-            a = L.PdsArgs()
-            a.dtype, a.fkind, a.hkind, a.gkind = L.PCS_F64 if f64 else L.PCS_F32, fk, spec['hkind'], spec['gkind']
-            a.n0, a.n1, a.row0, a.rows = n0, n1, 0, n0
-            a.kkind, a.edge = spec['kkind'], int(spec['edge'])
-            a.w0, a.w1 = spec['weights']
-            a.tau, a.sigma, a.rho, a.lam = float(tau), float(sigma), float(rho), spec['lam']
-            a.step0, a.step1 = spec['steps']
-            a.seg_a, a.seg_b = spec['seg']
-            a.x, a.xn = self.X[0].data_ptr(), self.X[1].data_ptr()
-            a.z, a.zn = self.Z[0].data_ptr(), self.Z[1].data_ptr()
+            a = _common_args(L.PdsArgs(), spec, dtype, tau, sigma, rho)
+            a.fkind = fk
+            self._bind(a, 0)
             a.partials = a.x  # placeholder for the support query (never written)
             if fk == L.PCS_F_DENOISE:
                 a.y = gsrc.data_ptr()
@@ -749,7 +670,7 @@ class PDS2DStencilEngine(PDS2DEngine):
                 a.gbuf = gsrc.data_ptr()
                 # separable PSF: grad F = N x - Conv^T y (the in-plane normal-operator kernel into the
                 # gradient buffer, then the march step), Conv^T y formed once here in fp64
-                sep = self.conv.separable(rtol=1e-13 if f64 else 2e-7)
+                sep = self.conv.separable(rtol=sep_rtol(dtype))
                 if sep is not None and sep[2] <= 7:
                     t0, t1, half = sep
                     self.taps = [torch.as_tensor(t).to(device=dev, dtype=dtype) for t in (t0, t1)]
@@ -772,39 +693,21 @@ class PDS2DStencilEngine(PDS2DEngine):
                         a.fkind, a.cty, a.ntaps = fk, None, None
                         self.nm_fused = False
                     else:
-                        fk = self.fkind = L.PCS_F_SEPCONV
+                        fk = L.PCS_F_SEPCONV
             if self.lib.pcs_pds2d_supported(ctypes.byref(a)) == 1:
                 self.march = True
             else:
                 a = None
-                fk = self.fkind = spec['fkind']
+                fk = spec['fkind']
         if a is None:
-            a = L.StencilArgs()
-            a.dtype = L.PCS_F32 if dtype == torch.float32 else L.PCS_F64
-            a.kkind, a.hkind, a.gkind, a.edge = spec['kkind'], spec['hkind'], spec['gkind'], int(spec['edge'])
-            a.n0, a.n1 = n0, n1
-            a.tau, a.sigma, a.rho, a.lam = float(tau), float(sigma), float(rho), spec['lam']
-            a.step0, a.step1 = spec['steps']
-            a.w0, a.w1 = spec['weights']
-            a.seg_a, a.seg_b = spec['seg']
+            a = _common_args(L.StencilArgs(), spec, dtype, tau, sigma, rho)
             a.fkind = fk
             if gsrc is not None:
                 a.g = gsrc.data_ptr()
-        self.args = a
-        nb_fn = self.lib.pcs_pds2d_nblocks if self.march else self.lib.pcs_pds2d_stencil_nblocks
-        ws_fn = self.lib.pcs_pds2d_ws_bytes if self.march else self.lib.pcs_pds2d_stencil_ws_bytes
-        self.nblocks = int(nb_fn(ctypes.byref(a)))
-        self._alloc_partials(a, dev)
-        self.ctrl = torch.zeros(int(self.lib.pcs_ctrl_bytes()) // 8, dtype=torch.float64, device=dev)
-        a.ctrl = self.ctrl.data_ptr()
-        self.fused_finalize = True
-        self.ws = torch.zeros(int(ws_fn(ctypes.byref(a))) // 8 + 2, dtype=torch.float64, device=dev)
-        a.ws = self.ws.data_ptr()
-        self.graph = None
-        self.hist = None
-        self.ctrl_host = torch.zeros(2, dtype=torch.int32).pin_memory()
-        self.native = fk != L.PCS_F_GRADBUF and self.N >= NATIVE_MIN_PIXELS
-        self.bar = None
+        lib = self.lib
+        self._init_loop_state(a, fk, lib.pcs_pds2d_nblocks if self.march else lib.pcs_pds2d_stencil_nblocks,
+                              lib.pcs_pds2d_ws_bytes if self.march else lib.pcs_pds2d_stencil_ws_bytes,
+                              fk != L.PCS_F_GRADBUF)
 
     def time_iteration_kernels(self, n):
         """As PDS2DEngine's; with a separable PSF (SEPCONV here) either the fused normal-operator
@@ -813,18 +716,12 @@ class PDS2DStencilEngine(PDS2DEngine):
         res = PDS2DEngine.time_iteration_kernels(self, n)
         if self.fkind == L.PCS_F_SEPCONV and not getattr(self, 'nm_fused', False):
             a, lib = self.args, self.lib
-            ev = []
+            timed = LaunchTimer()
             for i in range(min(n, 50)):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                L.check(lib.pcs_conv2d_sep_ata_planes(a.dtype, L.ptr(self.X[i % 2]), L.ptr(self.Gb), 1, a.n0, a.n1,
-                                                      L.ptr(self.taps[0]), 2 * a.half + 1, a.half,
-                                                      L.ptr(self.taps[1]), 2 * a.half + 1, a.half, L.stream()),
-                        'pcs_conv2d_sep_ata_planes')
-                e1.record()
-                ev.append((e0, e1))
-            torch.cuda.synchronize()
-            res['conv_nx'] = float(np.median([s.elapsed_time(e) for s, e in ev]))
+                timed('conv_nx', lambda: L.check(lib.pcs_conv2d_sep_ata_planes(
+                    a.dtype, L.ptr(self.X[i % 2]), L.ptr(self.Gb), 1, a.n0, a.n1, L.ptr(self.taps[0]), 2 * a.half + 1,
+                    a.half, L.ptr(self.taps[1]), 2 * a.half + 1, a.half, L.stream()), 'pcs_conv2d_sep_ata_planes'))
+            res.update(timed.result(np.median))
         return res
 
     def _step_call(self, st):
@@ -891,52 +788,22 @@ class PDS2DMaskEngine(PDS2DEngine):
     mask is False) and y expanded with NaN there; the solver's z = [z_m; z_s] is assembled on return."""
 
     def __init__(self, spec, dtype, tau, sigma, rho, x0, z0, chunk=32, use_graph=True):
-        self.lib = L.gpu()
-        self.spec = spec
-        self.dtype = dtype
-        n0, n1 = spec['shape']
-        self.N = N = n0 * n1
-        nc, m = spec['ncomp'], spec['m']
-        dev = x0.device
+        m = spec['m']
+        dev = self._init_state(spec, dtype, x0, z0[m:], chunk, use_graph, spec['ncomp'])
+        N = self.N
         self.idx = torch.as_tensor(np.flatnonzero(spec['mask']).astype(np.int64)).to(dev)
-        z0 = z0.to(dtype)
-        self.X = [x0.to(dtype).clone(), torch.empty(N, dtype=dtype, device=dev)]
-        self.Z = [z0[m:].clone(), torch.empty(nc * N, dtype=dtype, device=dev)]
         self.ZM = [torch.zeros(N, dtype=dtype, device=dev), torch.zeros(N, dtype=dtype, device=dev)]
-        self.ZM[0][self.idx] = z0[:m]
+        self.ZM[0][self.idx] = z0[:m].to(dtype)
         self.ym = torch.full((N,), float('nan'), dtype=dtype, device=dev)
         self.ym[self.idx] = -O.to_dev(spec['mask_shift'], dtype)  # y = -shift, exactly
-        self.chunk = max(2, chunk + (chunk % 2))
-        self.use_graph = use_graph
-        self.fkind = L.PCS_F_NULL
-        a = L.PdsArgs()
-        a.dtype = L.PCS_F64 if dtype == torch.float64 else L.PCS_F32
-        a.fkind, a.hkind, a.gkind = L.PCS_F_NULL, spec['hkind'], spec['gkind']
-        a.n0, a.n1, a.row0, a.rows = n0, n1, 0, n0
-        a.kkind, a.edge = spec['kkind'], int(spec['edge'])
-        a.w0, a.w1 = spec['weights']
-        a.tau, a.sigma, a.rho, a.lam = float(tau), float(sigma), float(rho), spec['lam']
-        a.step0, a.step1 = spec['steps']
-        a.seg_a, a.seg_b = spec['seg']
+        a = _common_args(L.PdsArgs(), spec, dtype, tau, sigma, rho)
+        a.fkind = L.PCS_F_NULL
         a.mkind, a.ym = L.PCS_M_L1LOSS, self.ym.data_ptr()
-        self.args = a
         self._bind(a, 0)
         a.partials = a.x  # placeholder for the support query (never written)
         if self.lib.pcs_pds2d_supported(ctypes.byref(a)) != 1:
             raise ValueError('masked data-fidelity problem not supported by the fused step')
-        self.nblocks = int(self.lib.pcs_pds2d_nblocks(ctypes.byref(a)))
-        self._alloc_partials(a, dev)
-        self.ctrl = torch.zeros(int(self.lib.pcs_ctrl_bytes()) // 8, dtype=torch.float64, device=dev)
-        a.ctrl = self.ctrl.data_ptr()
-        self.fused_finalize = True
-        self.ws = torch.zeros(int(self.lib.pcs_pds2d_ws_bytes(ctypes.byref(a))) // 8 + 2, dtype=torch.float64,
-                              device=dev)
-        a.ws = self.ws.data_ptr()
-        self.graph = None
-        self.hist = None
-        self.ctrl_host = torch.zeros(2, dtype=torch.int32).pin_memory()
-        self.native = self.N >= NATIVE_MIN_PIXELS
-        self.bar = None
+        self._init_loop_state(a, L.PCS_F_NULL, self.lib.pcs_pds2d_nblocks, self.lib.pcs_pds2d_ws_bytes, True)
 
     def _bind(self, a, p):
         PDS2DEngine._bind(self, a, p)

@@ -40,7 +40,8 @@ from ..func.penalty import L1Norm, L21Norm
 from ..linop.conv import Convolve1DOp
 from ..linop.diff import GradientOp
 from ..parallel.slab import SlabLayout
-from .engine import HIST_CHUNK, _half_loss_data, grow_hist
+from ._loop import LaunchTimer, LoopControl, capture_agreed
+from .engine import _half_loss_data
 
 
 def conv_chain(C, shape):
@@ -220,7 +221,7 @@ class PDS3DEngine:
             self.T.append(torch.empty_like(self.T[0]))
             self.gbuf = self.T[2]
         a = L.Pds3Args()
-        a.dtype = L.PCS_F32 if dtype == torch.float32 else L.PCS_F64
+        a.dtype = L.dtype_code(dtype)
         a.fkind, a.hkind, a.gkind = fk, spec['hkind'], spec['gkind']
         a.n0, a.n1, a.n2, a.plane0, a.planes = n0, n1, n2, self.row0, self.rows
         a.halo_x, a.halo_z, a.halo_g = hx, hz, hg
@@ -235,7 +236,7 @@ class PDS3DEngine:
         self.nblocks = int(self.lib.pcs_pds3d_nblocks(ctypes.byref(a)))
         self.partials = torch.empty(self.nblocks * 4, dtype=torch.float64, device=dev)
         a.partials = self.partials.data_ptr()
-        self.ctrl = torch.zeros(int(self.lib.pcs_ctrl_bytes()) // 8, dtype=torch.float64, device=dev)
+        self.ctl = LoopControl(dev)
         a.ctrl = self.ctrl.data_ptr()
         self.ws = torch.zeros(int(self.lib.pcs_pds3d_ws_bytes(ctypes.byref(a))) // 8 + 2, dtype=torch.float64,
                               device=dev)
@@ -285,11 +286,13 @@ class PDS3DEngine:
         self.halos = [lay.halo_pairs([(self.X[q], hx, 0)] + [(self.Z[q], hz, c, self.zdepth[c]) for c in range(3)])
                       for q in (0, 1)] if world > 1 else [{}, {}]
         self.halo_planes = hx + sum(self.zdepth)  # planes one side sends per iteration
-        self.hist = None
         self.graph = None
         self.chunk = max(2, chunk + chunk % 2)
         # graphs: one GPU, or the native RCCL transport (PCS_3D_GRAPH=0 launches eagerly)
         self.use_graph = use_graph and (world == 1 or (self.native_comm and os.environ.get('PCS_3D_GRAPH', '1') != '0'))
+
+    ctrl = property(lambda self: self.ctl.ctrl)
+    hist = property(lambda self: self.ctl.hist)
 
     def _args_for(self, p):
         b = L.Pds3Args()
@@ -472,9 +475,9 @@ class PDS3DEngine:
             cur, j = dst, j + 1
         assert cur is self.gbuf
 
-    def _step(self, p, hist):
+    def _step(self, p, hist, grad=True):
         st = L.stream()
-        if self.fkind == L.PCS_F_GRADBUF:
+        if grad and self.fkind == L.PCS_F_GRADBUF:
             self._gradient(p, st)
         a = self.args[p]
         a.hist = None if hist is None else hist.data_ptr()
@@ -531,17 +534,10 @@ class PDS3DEngine:
 
     # ---- loops
     def init_loop(self, max_iter, min_iter, accuracy_threshold, has_dual=True):
-        max_iter, min_iter = int(max_iter), int(min_iter)
-        total = max(min_iter, max_iter) + 1
-        self._total, self._issued = total, 0
-        hist_len = 2 * min(total, max(HIST_CHUNK, 2 * self.chunk)) + 2
-        if self.hist is None or self.hist.numel() < hist_len:
-            self.hist = torch.empty(hist_len, dtype=torch.float64, device=self.X[0].device)
+        total = self.ctl.start(max_iter, min_iter, accuracy_threshold, has_dual, chunk=self.chunk)
+        if self.ctl.replaced:  # the captured chunk holds the history pointer
             self.graph = None
-        self.hist.fill_(float('nan'))
-        L.check(self.lib.pcs_ctrl_init2(L.ptr(self.ctrl), int(min_iter), int(max_iter), float(accuracy_threshold),
-                                        int(has_dual), int(self.hist.numel()), L.stream()), 'pcs_ctrl_init2')
-        self._p = 0
+        self._issued, self._p = 0, 0
         return total
 
     def _chunk(self):
@@ -554,33 +550,18 @@ class PDS3DEngine:
         """Capture one chunk into a hipGraph.  Multi-GPU: every rank must end up with a graph or
         none (the captured RCCL calls pair across ranks), so the outcome is agreed collectively and
         a failed capture anywhere falls back to eager launches everywhere."""
-        torch.cuda.synchronize()
-        g, ok = torch.cuda.CUDAGraph(), True
-        try:
-            with torch.cuda.graph(g):
-                self._chunk()
-        except Exception:  # noqa: BLE001 -- torch's capture errors and the ABI's HipError alike: the
-            # flag all-gather below must run on every rank, or the others block in RCCL
-            ok, g = False, None
-            self._pending_ex = self._pending_ag = None  # handles of the aborted capture
-            torch.cuda.synchronize()
-        if self.world > 1:
-            flag = torch.tensor([1.0 if ok else 0.0], dtype=torch.float64, device=self.sums.device)
-            allf = torch.zeros(self.world, dtype=torch.float64, device=self.sums.device)
-            self.comm.allgather(flag, allf)
-            ok = bool(allf.min().item() > 0)
-        if not ok:
-            self.use_graph, g = False, None
-        self.graph = g
-        return ok
+        self.graph = capture_agreed(self._chunk, self.comm, self.world, self.sums.device)
+        if self.graph is None:
+            self.use_graph = False
+            self._pending_ex = self._pending_ag = None  # handles of an aborted capture
+        return self.graph is not None
 
     def advance(self, k):
         """Enqueue exactly k iterations: the schedule trial's (the first call with k >= 7 on a
         banded multi-GPU engine), then whole captured chunks from buffer parity 0, then eager
         iterations (a parity fix before the replays, the remainder after them)."""
-        grown = grow_hist(self.hist, self.ctrl, self._issued + k + 1, self._total)
-        if grown is not self.hist:  # the captured chunk holds the history pointer: recapture
-            self.hist, self.graph = grown, None
+        if self.ctl.reserve(self._issued + k + 2):  # the captured chunk holds the history pointer: recapture
+            self.graph = None
         self._issued += k
         if not self._tuned and self.banded and self.overlap and k >= 7:
             k -= self._autotune()  # eager, before any capture
@@ -637,10 +618,10 @@ class PDS3DEngine:
         return 7
 
     def iterations(self):
-        return int(self.ctrl.view(torch.int32)[0].item())
+        return self.ctl.iterations()
 
     def stopped(self):
-        return int(self.ctrl.view(torch.int32)[1].item()) != 0
+        return self.ctl.stopped()
 
     def result(self):
         """(n_iter, own planes of x, own planes of z (3 components), hist [n, 2])."""
@@ -649,8 +630,7 @@ class PDS3DEngine:
         q = n % 2
         x = self.lay.rows_view(self.X[q], self.hx, 0, self.rows).clone()
         z = torch.cat([self.lay.rows_view(self.Z[q], self.hz, 0, self.rows, c) for c in range(3)])
-        h = self.hist[:2 * n].cpu().numpy().reshape(n, 2) if n > 0 else np.zeros((0, 2))
-        return n, x, z, h
+        return n, x, z, self.ctl.rows(n)
 
     def run(self, max_iter, min_iter, accuracy_threshold, has_dual=True):
         total = self.init_loop(max_iter, min_iter, accuracy_threshold, has_dual)
@@ -670,52 +650,30 @@ class PDS3DEngine:
         init_loop(n + 1, ...) set it; call init_loop again before a measured run."""
         if self.world != 1:
             raise ValueError('time_parts: single-GPU engines only')
-        L.check(self.lib.pcs_ctrl_init2(L.ptr(self.ctrl), n + 1, n + 1, -1.0, 1, 2 * n + 6, L.stream()),
-                'pcs_ctrl_init2')
-        st = torch.cuda.current_stream()
-        ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
-        parts = {}
+        self._start_timed(n)
+        timed = LaunchTimer()
         for i in range(n):
             p = i % 2
-            marks = [('start', ev())]
-            marks[-1][1].record(st)
             if self.fkind == L.PCS_F_GRADBUF and self.fused0 and self.ata:
                 nsub = self.rows + 2 * self.hx
-                self._ata_planes(L.ptr(self.X[p]), L.ptr(self.T[0]), nsub, L.stream())
-                marks.append(('nrm', ev()))
-                marks[-1][1].record(st)
+                timed('nrm', lambda: self._ata_planes(L.ptr(self.X[p]), L.ptr(self.T[0]), nsub, L.stream()))
                 if not self.fold:
-                    self._g_range(self.g_lo, min(self.hx + self.rows + 1, nsub), L.stream())
-                    marks.append(('conv0', ev()))
-                    marks[-1][1].record(st)
+                    timed('conv0', lambda: self._g_range(self.g_lo, min(self.hx + self.rows + 1, nsub), L.stream()))
             elif self.fkind == L.PCS_F_GRADBUF:
-                self._gradient(p, L.stream())
-                marks.append(('gradient', ev()))
-                marks[-1][1].record(st)
-            a = self.args[p]
-            a.hist = None
-            L.check(self.lib.pcs_pds3d_step(ctypes.byref(a), L.stream()), 'pcs_pds3d_step')
-            marks.append(('step', ev()))
-            marks[-1][1].record(st)
-            parts.setdefault(i, marks)
-        torch.cuda.synchronize()
-        out = {}
-        for marks in parts.values():
-            for (_, e0), (name, e1) in zip(marks[:-1], marks[1:]):
-                out.setdefault(name, []).append(e0.elapsed_time(e1))
-        return {k: float(np.mean(v)) for k, v in out.items()}
+                timed('gradient', lambda: self._gradient(p, L.stream()))
+            timed('step', lambda: self._step(p, None, grad=False))
+        return timed.result()
+
+    def _start_timed(self, n):
+        """Loop state for n eager launches of the timers (which pass the step no history)."""
+        self.ctl.start_fixed(n + 1, n + 2)
+        if self.ctl.replaced:
+            self.graph = None
 
     def time_step_kernel(self, n):
         """Mean duration (ms) of pcs_pds3d_step alone over n eager launches (HIP events)."""
-        st = torch.cuda.current_stream()
-        L.check(self.lib.pcs_ctrl_init2(L.ptr(self.ctrl), n + 1, n + 1, -1.0, 1, 2 * n + 6, L.stream()),
-                'pcs_ctrl_init2')
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+        self._start_timed(n)
+        timed = LaunchTimer()
         for i in range(n):
-            a = self.args[i % 2]
-            a.hist = None
-            evs[i][0].record(st)
-            L.check(self.lib.pcs_pds3d_step(ctypes.byref(a), L.stream()), 'pcs_pds3d_step')
-            evs[i][1].record(st)
-        torch.cuda.synchronize()
-        return float(np.mean([s.elapsed_time(e) for s, e in evs]))
+            timed('step', lambda: self._step(i % 2, None, grad=False))
+        return timed.result()['step']

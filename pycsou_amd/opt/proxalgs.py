@@ -74,71 +74,51 @@ class _DeviceLoop:
     """Loop control of the per-operator (generic) path on the device: after each iteration the
     relative-improvement sums are reduced on the GPU (pcs_rel_sums) and pcs_pds_finalize
     records the diagnostics row and the reference loop condition (solver.py:65-66,
-    proxalgs.py:366-394) in a device control block -- the same one the fused engine uses.
-    The host learns the stop decision from an asynchronous copy of that block, up to ``lag``
-    iterations behind (no blocking .item() per iteration); iterations issued past the stop
-    are discarded by the caller, which keeps the last ``lag + 2`` states."""
-
-    # the device history starts at this many iterations and doubles as the loop issues more (a
-    # max_iter of 1e9 with accuracy_threshold doing the stopping must not allocate 16 GB up front)
-    HIST_CHUNK = 4096
+    proxalgs.py:366-394) in a device control block -- the same one the fused engines use
+    (``_loop.LoopControl``).  The host learns the stop decision from an asynchronous copy of that
+    block, up to ``lag`` iterations behind (no blocking .item() per iteration); iterations issued past
+    the stop are discarded by the caller, which keeps the last ``lag + 2`` states."""
 
     def __init__(self, max_iter, min_iter, thr, has_dual, device, lag=3, cap=None):
         from .. import _lib as L
+        from ._loop import LoopControl
         self.L, self.lib = L, L.gpu()
-        max_iter, min_iter = int(max_iter), int(min_iter)
-        self.total = max(min_iter, max_iter) + 1
-        cap = min(self.total, self.HIST_CHUNK) if cap is None else int(cap)  # cap: rows up front (graph chunks)
-        self.hist = torch.full((2 * cap + 2,), float('nan'), dtype=torch.float64, device=device)
-        self.ctrl = torch.zeros(int(self.lib.pcs_ctrl_bytes()) // 8, dtype=torch.float64, device=device)
+        self.ctl = LoopControl(device)
+        # cap: every history row up front (the graph chunks cannot grow it)
+        self.total = self.ctl.start(max_iter, min_iter, thr, has_dual, up_front=cap)
         self.sums = torch.zeros(4, dtype=torch.float64, device=device)
-        L.check(self.lib.pcs_ctrl_init2(L.ptr(self.ctrl), min_iter, max_iter, float(thr), int(has_dual),
-                                        int(self.hist.numel()), L.stream()), 'pcs_ctrl_init2')
         self.has_dual, self.lag = has_dual, lag
-        self.pending = []  # (pinned host copy of (it, stopped), event)
-        self.final = None
         self.issued = 0
 
-    def _grow(self):
-        """Before iteration `issued` is recorded: make room for its history row (and the stop test
-        of the next), doubling the device buffer and its length in the control block -- both
-        stream-ordered after every finalize already enqueued."""
-        need = 2 * (self.issued + 2) + 2
-        if need <= self.hist.numel():
-            return
-        cap = min(self.total, max(2 * ((self.hist.numel() - 2) // 2), self.issued + 2))
-        new = torch.full((2 * cap + 2,), float('nan'), dtype=torch.float64, device=self.hist.device)
-        new[:self.hist.numel()].copy_(self.hist)
-        self.hist = new
-        self.ctrl.view(torch.int32)[5].fill_(int(new.numel()))  # Ctrl.hist_len (pds_ctrl.hpp)
+    ctrl = property(lambda self: self.ctl.ctrl)
+    hist = property(lambda self: self.ctl.hist)
 
     def record(self, x_old, x, z_old=None, z=None):
         """Enqueue this iteration's sums + finalize and an async read-back of the control."""
-        O.rel_sums(x_old, x, self.sums[0:2])
-        if self.has_dual:
-            O.rel_sums(z_old, z, self.sums[2:4])
+        self._rel_sums(x_old, x, z_old, z)
         self.finalize()
 
     def finalize(self):
-        """The loop control of the iteration whose sums are in ``sums``, and its read-back."""
-        L = self.L
-        self._grow()
+        """The loop control of the iteration whose sums are in ``sums``, with room for its history row
+        (and the stop test of the next) made before it, and its read-back."""
+        self.ctl.reserve(self.issued + 2)
         self.issued += 1
-        L.check(self.lib.pcs_pds_finalize(L.ptr(self.sums), L.ptr(self.ctrl), L.ptr(self.hist), L.stream()),
-                'pcs_pds_finalize')
-        host = torch.empty(2, dtype=torch.int32, pin_memory=True)
-        host.copy_(self.ctrl.view(torch.int32)[:2], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.pending.append((host, ev))
+        self._finalize()
+        self.ctl.read_async()
 
     def record_captured(self, x_old, x, z_old=None, z=None):
         """``record`` inside a graph capture: the sums and the loop control only (no read-back, no
         growth -- the history holds every row up front, ``cap``)."""
-        L = self.L
+        self._rel_sums(x_old, x, z_old, z)
+        self._finalize()
+
+    def _rel_sums(self, x_old, x, z_old, z):
         O.rel_sums(x_old, x, self.sums[0:2])
         if self.has_dual:
             O.rel_sums(z_old, z, self.sums[2:4])
+
+    def _finalize(self):
+        L = self.L
         L.check(self.lib.pcs_pds_finalize(L.ptr(self.sums), L.ptr(self.ctrl), L.ptr(self.hist), L.stream()),
                 'pcs_pds_finalize')
 
@@ -157,22 +137,30 @@ class _DeviceLoop:
         self._shown = max(self._shown, done)
 
     def poll(self, drain=False):
-        """Resolve finished read-backs in order; returns the iteration count once the device
-        stopped (None while it runs).  Blocks only to keep at most ``lag`` in flight."""
-        while self.pending and self.final is None:
-            host, ev = self.pending[0]
-            if not (drain or len(self.pending) > self.lag or ev.query()):
-                break
-            ev.synchronize()
-            self.pending.pop(0)
-            self._emit(int(host[0]))
-            if int(host[1]) != 0:
-                self.final = int(host[0])
-        return self.final
+        """The iteration count once the device stopped (None while it runs); blocks only to keep at
+        most ``lag`` read-backs in flight."""
+        return self.ctl.poll(self.lag, drain, seen=self._emit)
 
     def rows(self, n):
-        h = self.hist[:2 * n].cpu().numpy().reshape(n, 2) if n > 0 else np.zeros((0, 2))
-        return h
+        return self.ctl.rows(n)
+
+
+def _drive(loop, state, step, record):
+    """The eager loop of the generic paths: issue iteration i (``step(i, previous state)``), enqueue its
+    diagnostics and loop control (``record(previous, new)``), keep the last ``lag + 3`` states and poll the
+    device's stop decision, which lags.  Returns (n, the state the reference loop ends with)."""
+    states = {-1: state}
+    i, n = 0, None
+    while n is None:
+        if i >= loop.total:
+            n = loop.poll(drain=True)
+            break
+        states[i] = step(i, states[i - 1])
+        record(states[i - 1], states[i])
+        states.pop(i - loop.lag - 3, None)
+        i += 1
+        n = loop.poll()
+    return n, states[n - 1]
 
 
 class PrimalDualSplitting(GenericIterativeAlgorithm):
@@ -357,29 +345,19 @@ class PrimalDualSplitting(GenericIterativeAlgorithm):
             if out is not None:
                 return out
         loop = _DeviceLoop(self.max_iter, self.min_iter, self.accuracy_threshold, bool(self._H),
-                           state['primal_variable'].device)
+                           state['primal_variable'].device, lag=self.LOOP_LAG)
         if self.verbose is not None:
             def show(k, h):
                 self._rows = [[k, h[0], h[1]] if self._H else [k, h[0]]]
                 self.print_diagnostics()
             loop.stream_rows(self.verbose, show)
-        states = {-1: state}
-        i, n = 0, None
-        while n is None:
-            if i >= loop.total:
-                n = loop.poll(drain=True)
-                break
-            new = self._update_dev(states[i - 1])
-            loop.record(states[i - 1]['primal_variable'], new['primal_variable'],
-                        states[i - 1]['dual_variable'], new['dual_variable'])
-            states[i] = new
-            states.pop(i - loop.lag - 3, None)
-            i += 1
-            n = loop.poll()
+        n, self._state = _drive(
+            loop, state, lambda i, st: self._update_dev(st),
+            lambda old, new: loop.record(old['primal_variable'], new['primal_variable'],
+                                         old['dual_variable'], new['dual_variable']))
         self.iter = n
         h = loop.rows(n)
         self._rows = [[k, h[k, 0], h[k, 1]] if self._H else [k, h[k, 0]] for k in range(n)]
-        self._state = states[n - 1]
         self.converged = True
         cols = ['Iter', 'Relative Improvement (primal variable)']
         if self._H:
@@ -389,6 +367,8 @@ class PrimalDualSplitting(GenericIterativeAlgorithm):
                         'dual_variable': self._out(self._state['dual_variable'])}
         return self.iterand, self.converged, self.diagnostics
 
+    # read-backs of the loop control the eager generic loop keeps in flight (0: it waits for every iteration's)
+    LOOP_LAG = 3
     # iterations per captured chunk of the generic path; the state ring holds two chunks
     GRAPH_CHUNK = 4
     GRAPH_RING_BYTES = 8 << 30
@@ -439,7 +419,7 @@ class PrimalDualSplitting(GenericIterativeAlgorithm):
                         self._update_dev({'primal_variable': X[prev], 'dual_variable': Z[prev]},
                                          out=(X[slot], Z[slot] if self._H else None))
                         loop.record_captured(X[prev], X[slot], Z[prev], Z[slot])
-                    host[h].copy_(loop.ctrl.view(torch.int32)[:2], non_blocking=True)
+                    loop.ctl.fetch(host[h])  # captured: each graph keeps its own fixed pinned pair
                 pool = g.pool()
                 graphs.append(g)
         except Exception:  # noqa: BLE001 -- torch's capture errors and the ABI's HipError alike
@@ -620,7 +600,7 @@ class AcceleratedProximalGradientDescent(GenericIterativeAlgorithm):
         import ctypes
         from .. import _lib as L
         a = L.Apgd2dArgs()
-        a.dtype = L.PCS_F32 if dtype == torch.float32 else L.PCS_F64
+        a.dtype = L.dtype_code(dtype)
         a.gkind, (a.n0, a.n1), a.half = spec['gkind'], spec['shape'], spec['sep'][2]
         a.tau, a.lam = 1.0, 1.0
         for i, f in enumerate(('taps0', 'taps1', 'x', 'xn', 'aux', 'aux_n', 'cty')):
@@ -664,25 +644,20 @@ class AcceleratedProximalGradientDescent(GenericIterativeAlgorithm):
                 self._rows = [[k, h[0]]]
                 self.print_diagnostics()
             loop.stream_rows(self.verbose, show)
-        states = {-1: (x0, torch.zeros_like(x0), 1)}
-        i, n = 0, None
-        while n is None:
-            if i >= loop.total:
-                n = loop.poll(drain=True)
-                break
+
+        def step(i, st):
             self.iter = i  # the 'CD' momentum reads the iteration index (proxalgs.py:596-598)
-            new = self._update_dev(states[i - 1], sums_out=loop.sums[0:2])
+            return self._update_dev(st, sums_out=loop.sums[0:2])
+
+        def record(old, new):
             if self._sums is None:
-                O.rel_sums(states[i - 1][0], new[0], loop.sums[0:2])
+                O.rel_sums(old[0], new[0], loop.sums[0:2])
             loop.finalize()
-            states[i] = new
-            states.pop(i - loop.lag - 3, None)
-            i += 1
-            n = loop.poll()
+
+        n, self._state = _drive(loop, (x0, torch.zeros_like(x0), 1), step, record)
         self.iter = n
         h = loop.rows(n)
         self._rows = [[k, h[k, 0]] for k in range(n)]
-        self._state = states[n - 1]
         self.converged = True
         self.diagnostics = _frame(['Iter', 'Relative Improvement'], self._rows)
         x, aux, t = self._state

@@ -37,6 +37,7 @@ import torch
 import torch.distributed as dist
 
 from .. import _lib as L
+from ..opt._loop import LaunchTimer, LoopControl, capture_agreed
 from ..opt.engine import nmarch_taps
 from .. import _ops as O
 
@@ -323,7 +324,7 @@ class SlabPDS2D:
         nc = spec.get('ncomp', 2)
         self.ncomp = nc
         a = L.PdsArgs()
-        a.dtype = L.PCS_F32 if dtype == torch.float32 else L.PCS_F64
+        a.dtype = L.dtype_code(dtype)
         a.hkind, a.gkind = spec['hkind'], spec['gkind']
         a.n0, a.n1, a.row0, a.rows = n0, n1, self.row0, self.rows
         a.tau, a.sigma, a.rho, a.lam = float(tau), float(sigma), float(rho), spec['lam']
@@ -443,12 +444,11 @@ class SlabPDS2D:
         a.hist, a.ws = None, None
         self.sums = torch.zeros(4, dtype=torch.float64, device=dev)
         self.gathered = torch.zeros(4 * world, dtype=torch.float64, device=dev)
-        self.ctrl = torch.zeros(int(self.lib.pcs_ctrl_bytes()) // 8, dtype=torch.float64, device=dev)
+        self.ctl = LoopControl(dev)
         a.ctrl = self.ctrl.data_ptr()
         self.args = [self._args_for(a, p) for p in range(self.nbuf)]
         self.halos = [lay.halo_pairs([(self.X[q], hx, 0)] + [(self.Z[q], hz, c) for c in range(nc)])
                       for q in range(self.nbuf)]
-        self.hist = None
         self.chunk = max(1, int(chunk))
         # native loop (pcs_slab2d_run): one C call per chunk instead of five Python-issued
         # operations per iteration; needs an RCCL communicator when world > 1
@@ -477,6 +477,9 @@ class SlabPDS2D:
         gc = int(os.environ.get('PCS_SLAB_GRAPH', '32' if world > 1 else '0') or 0)
         self.graph_chunk = (gc + gc % 2) if self.native and gc > 0 else 0
         self._graph = None
+
+    ctrl = property(lambda self: self.ctl.ctrl)
+    hist = property(lambda self: self.ctl.hist)
 
     def _padded(self, t):
         """t inside a buffer with self.pad zero rows before and after it (the view keeps the storage alive);
@@ -542,8 +545,6 @@ class SlabPDS2D:
         return hs
 
     def _native_plan(self):
-        if self.hist is None:
-            self.hist = torch.full((2,), float('nan'), dtype=torch.float64, device=self.X[0].device)
         key = (self.hist.data_ptr(), self.overlap)
         if self._plan is not None and self._plan_key == key:
             return self._plan
@@ -565,8 +566,6 @@ class SlabPDS2D:
 
     def _deep_plan(self):
         """The communication-avoiding plan (pcs_slab2d_deep_create) of a depth > 1 slab."""
-        if self.hist is None:
-            self.hist = torch.full((2,), float('nan'), dtype=torch.float64, device=self.X[0].device)
         key = (self.hist.data_ptr(),)
         if self._deep is not None and self._deep_key == key:
             return self._deep
@@ -650,13 +649,9 @@ class SlabPDS2D:
 
     # ---- loops
     def init_loop(self, max_iter, min_iter, accuracy_threshold, has_dual=True):
-        total = max(min_iter, max_iter) + 1
-        hist_len = 2 * total + 2
-        if self.hist is None or self.hist.numel() < hist_len:
-            self.hist = torch.empty(hist_len, dtype=torch.float64, device=self.X[0].device)
-        self.hist.fill_(float('nan'))
-        L.check(self.lib.pcs_ctrl_init2(L.ptr(self.ctrl), int(min_iter), int(max_iter), float(accuracy_threshold),
-                                        int(has_dual), int(self.hist.numel()), L.stream()), 'pcs_ctrl_init2')
+        # every row up front: the native plans hold the history pointer
+        total = max(int(min_iter), int(max_iter)) + 1
+        self.ctl.start(max_iter, min_iter, accuracy_threshold, has_dual, up_front=total)
         self._p = 0
         self._b = 0
         return total
@@ -694,24 +689,12 @@ class SlabPDS2D:
             self._p, k = 0, k - 1
         if self._graph is None:
             plan = self._native_plan()
-            torch.cuda.synchronize()
-            g, ok = torch.cuda.CUDAGraph(), True
-            try:
-                with torch.cuda.graph(g):
-                    L.check(self.lib.pcs_slab2d_run(plan, c, 0, L.stream()), 'pcs_slab2d_run')
-            except Exception:  # noqa: BLE001 -- torch's capture errors and HipError alike: every rank
-                # must reach the flag all-gather below, or the others block in RCCL
-                ok, g = False, None
-                torch.cuda.synchronize()
-            if self.world > 1:
-                flag = torch.tensor([1.0 if ok else 0.0], dtype=torch.float64, device=self.sums.device)
-                allf = torch.zeros(self.world, dtype=torch.float64, device=self.sums.device)
-                self.comm.allgather(flag, allf)
-                ok = bool(allf.min().item() > 0)
-            if not ok:
+            self._graph = capture_agreed(
+                lambda: L.check(self.lib.pcs_slab2d_run(plan, c, 0, L.stream()), 'pcs_slab2d_run'),
+                self.comm, self.world, self.sums.device)
+            if self._graph is None:
                 self.graph_chunk = 0
                 return k
-            self._graph = g
         while k >= c:
             self._graph.replay()
             k -= c
@@ -748,10 +731,10 @@ class SlabPDS2D:
         return 8
 
     def stopped(self):
-        return int(self.ctrl.view(torch.int32)[1].item()) != 0
+        return self.ctl.stopped()
 
     def iterations(self):
-        return int(self.ctrl.view(torch.int32)[0].item())
+        return self.ctl.iterations()
 
     def result(self):
         """(n_iter, own rows of x, own rows of z (2 components), hist [n, 2])."""
@@ -760,8 +743,7 @@ class SlabPDS2D:
         q = n % self.nbuf
         x = self.lay.rows_view(self.X[q], self.hx, 0, self.rows).clone()
         z = torch.cat([self.lay.rows_view(self.Z[q], self.hz, 0, self.rows, c) for c in range(self.ncomp)])
-        h = self.hist[:2 * n].cpu().numpy().reshape(n, 2) if n > 0 else np.zeros((0, 2))
-        return n, x, z, h
+        return n, x, z, self.ctl.rows(n)
 
     def run(self, max_iter, min_iter, accuracy_threshold, has_dual=True):
         """The reference loop (solver.py:65-76) across all ranks: every rank holds the
@@ -779,16 +761,12 @@ class SlabPDS2D:
     def time_step_kernel(self, n):
         """Average duration (ms) of the slab step kernel over n eager launches (HIP events
         on the launching stream); leaves x/z advanced by n iterations of ping-pong."""
-        st = torch.cuda.current_stream()
-        L.check(self.lib.pcs_ctrl_init2(L.ptr(self.ctrl), n + 1, n + 1, -1.0, 1, 2 * n + 6, L.stream()),
-                'pcs_ctrl_init2')
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+        self.ctl.start_fixed(n + 1, n + 2)
+        timed = LaunchTimer()
         for i in range(n):
-            evs[i][0].record(st)
-            L.check(self.lib.pcs_pds2d_step(ctypes.byref(self.args[i % 2]), L.stream()), 'pcs_pds2d_step')
-            evs[i][1].record(st)
-        torch.cuda.synchronize()
-        return float(np.mean([s.elapsed_time(e) for s, e in evs]))
+            timed('step', lambda: L.check(self.lib.pcs_pds2d_step(ctypes.byref(self.args[i % 2]), L.stream()),
+                                          'pcs_pds2d_step'))
+        return timed.result()['step']
 
 
 def comm_probe(eng, reps=5):

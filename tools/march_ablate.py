@@ -34,11 +34,10 @@ def child():
     N = 200
     eng.prepare_fixed(4 * N + 10, 2)
     a = eng.args
-    a.hist = eng.hist.data_ptr() if eng.fused_finalize else None
+    a.hist = eng.hist.data_ptr()
 
     def b2b(k):
-        L.check(eng.lib.pcs_ctrl_init2(L.ptr(eng.ctrl), k + 1, k + 1, -1.0, 1, int(eng.hist.numel()), L.stream()),
-                'init')
+        eng.ctl.start_fixed(k + 1)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for i in range(k):

@@ -39,7 +39,7 @@ def main():
     print(f'eager+events: {eng.time_step_kernel(N) * 1e3:.1f} us/launch', flush=True)
     # eager back-to-back (fresh loop state, no events between launches)
     a = eng.args
-    L.check(eng.lib.pcs_ctrl_init2(L.ptr(eng.ctrl), N + 1, N + 1, -1.0, 1, int(eng.hist.numel()), L.stream()), 'init')
+    eng.ctl.start_fixed(N + 1)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for i in range(N):
