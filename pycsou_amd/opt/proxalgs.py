@@ -396,21 +396,23 @@ class PrimalDualSplitting(GenericIterativeAlgorithm):
         R = 2 * C
         x0, z0 = state['primal_variable'], state['dual_variable']
         total = max(int(self.max_iter), int(self.min_iter)) + 1
-        loop = _DeviceLoop(self.max_iter, self.min_iter, self.accuracy_threshold, bool(self._H), x0.device,
-                           cap=total + R + 2)
-        X = [torch.empty_like(x0) for _ in range(R)]
-        Z = [None if z0 is None else torch.empty_like(z0) for _ in range(R)]
-        X[R - 1].copy_(x0)
-        if z0 is not None:
-            Z[R - 1].copy_(z0)
-        # one eager iteration and reduction first (discarded): lazy library state (plans, workspaces) is
-        # created outside the capture
-        self._update_dev({'primal_variable': X[R - 1], 'dual_variable': Z[R - 1]})
-        O.rel_sums(X[R - 1], X[R - 1], loop.sums[0:2])
-        host = [torch.zeros(2, dtype=torch.int32, pin_memory=True) for _ in range(2)]
-        torch.cuda.synchronize()
         graphs, pool = [], None
         try:
+            # the history, the state ring and the pinned pair are allocated inside the try: running out of
+            # memory here falls back to the eager loop (which needs one state, not 2C) like a failed capture
+            loop = _DeviceLoop(self.max_iter, self.min_iter, self.accuracy_threshold, bool(self._H), x0.device,
+                               cap=total + R + 2)
+            X = [torch.empty_like(x0) for _ in range(R)]
+            Z = [None if z0 is None else torch.empty_like(z0) for _ in range(R)]
+            X[R - 1].copy_(x0)
+            if z0 is not None:
+                Z[R - 1].copy_(z0)
+            # one eager iteration and reduction first (discarded): lazy library state (plans, workspaces) is
+            # created outside the capture
+            self._update_dev({'primal_variable': X[R - 1], 'dual_variable': Z[R - 1]})
+            O.rel_sums(X[R - 1], X[R - 1], loop.sums[0:2])
+            host = [torch.zeros(2, dtype=torch.int32, pin_memory=True) for _ in range(2)]
+            torch.cuda.synchronize()
             for h in range(2):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, pool=pool):
