@@ -4,6 +4,8 @@ the host's asynchronous view of the stop decision (the reference's ``while`` of
 ``pycsou/core/solver.py:65-66`` runs on the device; the host only learns about the stop afterwards).
 """
 
+import ctypes
+
 import numpy as np
 import torch
 
@@ -128,6 +130,44 @@ class LoopControl:
             if stopped != 0:
                 self.final = it
         return self.final
+
+
+class LoopViews:
+    """The control block and the history of the LoopControl an object holds as `ctl`."""
+
+    ctrl = property(lambda self: self.ctl.ctrl)
+    hist = property(lambda self: self.ctl.hist)
+
+
+class LoopState(LoopViews):
+    """What an engine whose step reduces and finalizes its own diagnostics holds of its loop on the
+    device, beside the iterates: the LoopControl `ctl`, the per-workgroup norm partials and the
+    workspace of the in-kernel reduce + finalize."""
+
+    def _init_reduction(self, a, dev, nblocks_fn, ws_bytes_fn):
+        """The step arguments `a` are complete but for what the loop owns: the partials of the launch's
+        `nblocks_fn(a)` workgroups, the loop control, and the reduction workspace of `ws_bytes_fn(a)` bytes
+        (its counters start at 0 and every launch leaves them at 0)."""
+        self.nblocks = int(nblocks_fn(ctypes.byref(a)))
+        self._alloc_partials(a, dev)
+        self.ctl = LoopControl(dev)
+        a.ctrl = self.ctrl.data_ptr()
+        self.ws = torch.zeros(int(ws_bytes_fn(ctypes.byref(a))) // 8 + 2, dtype=torch.float64, device=dev)
+        a.ws = self.ws.data_ptr()
+
+    def _alloc_partials(self, a, dev):
+        """[nblocks][4] doubles."""
+        self.partials = torch.empty(4 * self.nblocks, dtype=torch.float64, device=dev)
+        a.partials = self.partials.data_ptr()
+
+
+def worst_over_ranks(comm, values, world, device):
+    """Max over ranks of each of this rank's (at most 4) timings, so that every rank takes the same
+    decision from them: one all-gather of 4 doubles per rank."""
+    mine = torch.tensor(list(values) + [0.0] * (4 - len(values)), dtype=torch.float64, device=device)
+    allt = torch.zeros(4 * world, dtype=torch.float64, device=device)
+    comm.allgather(mine, allt)
+    return allt.view(world, 4).max(dim=0).values[:len(values)].tolist()
 
 
 def capture_agreed(fn, comm=None, world=1, device=None):

@@ -17,6 +17,7 @@ device, so a replay after convergence is a sequence of no-op launches and the
 iteration count is exactly the reference's.
 """
 
+import collections
 import ctypes
 import os
 
@@ -32,7 +33,7 @@ from ..func.penalty import L1Norm, L21Norm, SquaredL2Norm
 from ..linop.base import HomothetyMap
 from ..linop.conv import Convolve2DOp
 from ..linop.diff import GradientOp, LaplacianOp
-from ._loop import LaunchTimer, LoopControl
+from ._loop import LaunchTimer, LoopState
 
 # images at least this large launch chunks from C instead of replaying a captured graph
 NATIVE_MIN_PIXELS = int(os.environ.get('PCS_NATIVE_MIN_PIXELS', 1 << 20))
@@ -52,31 +53,62 @@ def _half_loss_data(F):
     return None
 
 
-def _match_g(G, spec):
-    """G = None / NullProximableFunctional / NonNegativeOrthant / Segment -> spec['gkind'], spec['seg']."""
+def match_g(G):
+    """G = None / NullProximableFunctional / NonNegativeOrthant / Segment -> {'gkind', 'seg'} or None."""
     if G is None or isinstance(G, NullProximableFunctional):
-        spec['gkind'], spec['seg'] = L.PCS_G_NULL, (0.0, 1.0)
-    elif isinstance(G, IndicatorFunctional) and G.kind == 'nonneg':
-        spec['gkind'], spec['seg'] = L.PCS_G_NONNEG, (0.0, 1.0)
-    elif isinstance(G, IndicatorFunctional) and G.kind == 'segment':
-        spec['gkind'], spec['seg'] = L.PCS_G_SEGMENT, G.params
-    else:
-        return False
-    return True
+        return {'gkind': L.PCS_G_NULL, 'seg': (0.0, 1.0)}
+    if isinstance(G, IndicatorFunctional) and G.kind == 'nonneg':
+        return {'gkind': L.PCS_G_NONNEG, 'seg': (0.0, 1.0)}
+    if isinstance(G, IndicatorFunctional) and G.kind == 'segment':
+        return {'gkind': L.PCS_G_SEGMENT, 'seg': G.params}
+    return None
 
 
-def _match_h(H, ncomp, N):
-    """H = lam * (L1Norm | L21Norm over the ncomp components of each pixel) -> (hkind, lam) or None."""
+def match_h(H, ncomp, N):
+    """H = lam * (L1Norm | L21Norm over the ncomp components of each pixel) -> {'hkind', 'lam'} or None."""
     base, lam = H, 1.0
     if isinstance(H, ProxFuncPostComp):
         if H.shift != 0:
             return None
         base, lam = H.prox_func, float(H.scale)
     if ncomp > 1 and isinstance(base, L21Norm) and base.pixel_d == ncomp and base.dim == ncomp * N:
-        return L.PCS_H_L21, lam
+        return {'hkind': L.PCS_H_L21, 'lam': lam}
     if isinstance(base, L1Norm) and base.dim == ncomp * N:
-        return L.PCS_H_L1, lam
+        return {'hkind': L.PCS_H_L1, 'lam': lam}
     return None
+
+
+def match_f(F, N, conv_of, conv_fkind, conv_key='conv'):
+    """F = 0, (1/2) SquaredL2Loss(y) on N samples, or that composed with the problem's convolution ->
+    {'fkind'[, 'shift'[, conv_key]]} or None.  `conv_of(op)`: what the engine keeps of `op` when it is a
+    convolution of this problem (a Convolve2DOp on the image, a chain of Convolve1D on the volume), else
+    None; such an F gets `conv_fkind`."""
+    if F is None or isinstance(F, NullDifferentiableFunctional):
+        return {'fkind': L.PCS_F_NULL}
+    s = _half_loss_data(F)
+    if s is not None and O.numel(s) == N:
+        return {'fkind': L.PCS_F_DENOISE, 'shift': s}
+    if isinstance(F, DiffMapComp):
+        conv, s = conv_of(F.map2), _half_loss_data(F.map1)
+        if conv and s is not None and O.numel(s) == N:
+            return {'fkind': conv_fkind, 'shift': s, conv_key: conv}
+    return None
+
+
+def conv2d_on(shape):
+    """match_f's `conv_of` of the 2-D problems: a Convolve2DOp on `shape`."""
+    return lambda op: op if isinstance(op, Convolve2DOp) and op.dims == shape else None
+
+
+def fused_spec(head, *parts):
+    """The K-specific entries `head` and the matched H, G and F entries as one spec; None when any
+    of them did not match."""
+    if any(p is None for p in parts):
+        return None
+    spec = dict(head)
+    for p in parts:
+        spec.update(p)
+    return spec
 
 
 def nmarch_taps(t0, t1, half, dtype=np.float32):
@@ -138,26 +170,9 @@ def match_stencil2d(F, G, H, K, has_H):
         return None
     shape = tuple(K.dims)
     N = shape[0] * shape[1]
-    hm = _match_h(H, ncomp, N)
-    if hm is None:
-        return None
-    spec = {'stencil': True, 'shape': shape, 'steps': tuple(K.steps), 'kkind': kk, 'ncomp': ncomp,
-            'weights': w, 'edge': bool(K.edge), 'hkind': hm[0], 'lam': hm[1]}
-    if not _match_g(G, spec):
-        return None
-    if F is None or isinstance(F, NullDifferentiableFunctional):
-        spec['fkind'] = L.PCS_F_NULL
-        return spec
-    s = _half_loss_data(F)
-    if s is not None and O.numel(s) == N:
-        spec['fkind'], spec['shift'] = L.PCS_F_DENOISE, s
-        return spec
-    if isinstance(F, DiffMapComp) and isinstance(F.map2, Convolve2DOp) and F.map2.dims == shape:
-        s = _half_loss_data(F.map1)
-        if s is not None and O.numel(s) == N:
-            spec['fkind'], spec['shift'], spec['conv'] = L.PCS_F_GRADBUF, s, F.map2
-            return spec
-    return None
+    head = {'stencil': True, 'shape': shape, 'steps': tuple(K.steps), 'kkind': kk, 'ncomp': ncomp,
+            'weights': w, 'edge': bool(K.edge)}
+    return fused_spec(head, match_h(H, ncomp, N), match_g(G), match_f(F, N, conv2d_on(shape), L.PCS_F_GRADBUF))
 
 
 def match_pds2d(F, G, H, K, has_H):
@@ -166,36 +181,8 @@ def match_pds2d(F, G, H, K, has_H):
         return None
     shape = K.dims
     N = shape[0] * shape[1]
-    spec = {'shape': shape, 'steps': tuple(K.steps)}
-    # H = lam * (L1 | L21 pixel groups)
-    base, lam = H, 1.0
-    if isinstance(H, ProxFuncPostComp):
-        if H.shift != 0:
-            return None
-        base, lam = H.prox_func, float(H.scale)
-    if isinstance(base, L21Norm) and base.pixel_d == 2 and base.dim == 2 * N:
-        spec['hkind'] = L.PCS_H_L21
-    elif isinstance(base, L1Norm) and base.dim == 2 * N:
-        spec['hkind'] = L.PCS_H_L1
-    else:
-        return None
-    spec['lam'] = lam
-    if not _match_g(G, spec):
-        return None
-    # F
-    if F is None or isinstance(F, NullDifferentiableFunctional):
-        spec['fkind'] = L.PCS_F_NULL
-        return spec
-    s = _half_loss_data(F)
-    if s is not None and O.numel(s) == N:
-        spec['fkind'], spec['shift'] = L.PCS_F_DENOISE, s
-        return spec
-    if isinstance(F, DiffMapComp) and isinstance(F.map2, Convolve2DOp) and F.map2.dims == shape:
-        s = _half_loss_data(F.map1)
-        if s is not None and O.numel(s) == N:
-            spec['fkind'], spec['shift'], spec['conv'] = L.PCS_F_SEPCONV, s, F.map2
-            return spec
-    return None
+    return fused_spec({'shape': shape, 'steps': tuple(K.steps)}, match_h(H, 2, N), match_g(G),
+                      match_f(F, N, conv2d_on(shape), L.PCS_F_SEPCONV))
 
 
 def apgd_g_kind(G):
@@ -204,15 +191,10 @@ def apgd_g_kind(G):
     lam = 1.0
     if isinstance(G, ProxFuncPostComp) and G.shift == 0 and isinstance(G.prox_func, L1Norm):
         G, lam = G.prox_func, float(G.scale)
-    if G is None or isinstance(G, NullProximableFunctional):
-        return L.PCS_G_NULL, 1.0, (0.0, 1.0)
     if isinstance(G, L1Norm):
         return L.PCS_APGD_G_L1, lam, (0.0, 1.0)
-    if isinstance(G, IndicatorFunctional) and G.kind == 'nonneg':
-        return L.PCS_G_NONNEG, 1.0, (0.0, 1.0)
-    if isinstance(G, IndicatorFunctional) and G.kind == 'segment':
-        return L.PCS_G_SEGMENT, 1.0, tuple(G.params)
-    return None
+    g = match_g(G)
+    return None if g is None else (g['gkind'], 1.0, tuple(g['seg']))
 
 
 def sep_rtol(dtype):
@@ -262,7 +244,97 @@ def apgd_coeffs(acceleration, d, k0, n, t_old):
     return out, t_old
 
 
-class APGD2DEngine:
+def with_fields(a, **fields):
+    """A copy of the argument struct `a` with `fields` set: a candidate or a query never touches the
+    struct an engine launches with, so nothing is saved and restored."""
+    b = type(a)()
+    ctypes.pointer(b)[0] = a
+    for k, v in fields.items():
+        setattr(b, k, v)
+    return b
+
+
+def query(fn, a, *rest, **fields):
+    """fn(a with `fields`, *rest) for a planning entry point of the library (support, path, block
+    counts).  Those launch nothing and dereference nothing, but they look at which pointers are set and
+    how they are aligned: a pointer the loop binds or allocates later is given an address the engine
+    already holds (or, on a host without a GPU, any 16-byte-aligned number) as a placeholder for the
+    query."""
+    return fn(ctypes.byref(with_fields(a, **fields)), *rest)
+
+
+def step_args(spec, dtype, tau, sigma, rho, lay=None, cls=L.PdsArgs, with_k=True):
+    """The scalar fields of a 2-D step's arguments (pcs_pds2d_args, or `cls` = pcs_pds2d_stencil_args,
+    which share them by name) from a spec and the step sizes; `lay`: the SlabLayout of a row slab.
+    `with_k`: K's kind, edge rule and weights from the spec, which only the general-stencil specs carry."""
+    a = cls()
+    a.dtype = L.dtype_code(dtype)
+    a.hkind, a.gkind = spec['hkind'], spec['gkind']
+    a.n0, a.n1 = spec['shape']
+    a.tau, a.sigma, a.rho, a.lam = float(tau), float(sigma), float(rho), spec['lam']
+    a.step0, a.step1 = spec['steps']
+    a.seg_a, a.seg_b = spec['seg']
+    if lay is not None:
+        # Inherited difference, kept field for field: a slab states K in full, and for a spec of
+        # match_pds2d (which carries no K) with the forward Gradient's own values -- edge True, weights
+        # (1, 1) -- where the whole-image forward engine (`with_k` False below) leaves kkind, edge, w0 and
+        # w1 at 0.  The forward-Gradient kernels read none of them.
+        a.row0, a.rows = lay.row0, lay.rows
+        a.kkind, a.edge = spec.get('kkind', L.PCS_K_GRAD_FORWARD), int(spec.get('edge', True))
+        a.w0, a.w1 = spec.get('weights', (1.0, 1.0))
+        return a
+    if with_k:
+        a.kkind, a.edge = spec['kkind'], int(spec['edge'])
+        a.w0, a.w1 = spec['weights']
+    if cls is L.PdsArgs:  # one slab, the whole image: no halos
+        a.row0, a.rows = 0, a.n0
+    return a
+
+
+class SepPSF:
+    """The device operands of a separable PSF in the compute dtype: `taps` (axis 0, axis 1) of half width
+    `half`; after normal() those of grad F = N x - Conv^T y as well: the tables `ntaps` of
+    N = Conv^T Conv (nmarch_taps) and `cty` = Conv^T y."""
+
+    @classmethod
+    def of(cls, spec, dtype, dev, max_half=None):
+        """The operands of the spec's PSF; None when it is not rank one to sep_rtol(dtype) or reaches
+        more than `max_half` samples either side."""
+        sep = spec['sep'] if 'sep' in spec else spec['conv'].separable(rtol=sep_rtol(dtype))
+        if sep is None or (max_half is not None and sep[2] > max_half):
+            return None
+        return cls(sep, spec, dtype, dev)
+
+    def __init__(self, sep, spec, dtype, dev):
+        self.sep, self.spec, self.dtype, self.dev = sep, spec, dtype, dev
+        self.half = sep[2]
+        self.taps = [torch.as_tensor(t).to(device=dev, dtype=dtype) for t in sep[:2]]
+        self.ntaps = self.cty = None
+
+    def normal(self, cty64=None, tables=True):
+        """Conv^T y formed once in fp64 (y = -shift exactly; `cty64`: a slab's window of it) and cast,
+        and with `tables` the N tables in the compute dtype (the fp64 march reads them in fp64)."""
+        t0, t1, half = self.sep
+        if tables:
+            np_dtype = np.float64 if self.dtype == torch.float64 else np.float32
+            self.ntaps = torch.as_tensor(nmarch_taps(t0, t1, half, np_dtype)).to(self.dev)
+        if cty64 is None:
+            cty64 = self.spec['conv']._adj(-O.to_dev(self.spec['shift'], torch.float64))
+        self.cty = cty64.to(self.dtype).contiguous()
+        return self
+
+    def attach(self, eng, a):
+        """The operands as the engine's `taps`, `cty`, `ntaps` and in its step arguments."""
+        eng.taps, eng.cty, eng.ntaps = self.taps, self.cty, self.ntaps
+        a.half = self.half
+        a.taps0, a.taps1 = self.taps[0].data_ptr(), self.taps[1].data_ptr()
+        if self.cty is not None:
+            a.cty = self.cty.data_ptr()
+        if self.ntaps is not None:
+            a.ntaps = self.ntaps.data_ptr()
+
+
+class APGD2DEngine(LoopState):
     """Device state + loop of one fused 2-D APGD problem (match_apgd2d): every iteration is ONE launch
     (pcs_apgd2d_step: grad F by the two-pass normal-operator march, G.prox, the momentum step, the
     diagnostics' norms and the loop test), launched from C in chunks (pcs_apgd2d_run) with the chunk's
@@ -279,32 +351,18 @@ class APGD2DEngine:
         self.X = [torch.empty(self.N, dtype=dtype, device=dev) for _ in range(2)]
         self.AUX = [torch.empty(self.N, dtype=dtype, device=dev) for _ in range(2)]
         self.chunk = max(2, chunk + (chunk % 2))
-        t0, t1, half = spec['sep']
-        self.taps = [torch.as_tensor(t).to(device=dev, dtype=dtype) for t in (t0, t1)]
-        # Conv^T y formed once in fp64 (y = -shift exactly)
-        self.cty = spec['conv']._adj(-O.to_dev(spec['shift'], torch.float64)).to(dtype).contiguous()
         a = L.Apgd2dArgs()
         a.dtype = L.dtype_code(dtype)
-        a.gkind, a.n0, a.n1, a.half = spec['gkind'], n0, n1, half
-        a.taps0, a.taps1 = self.taps[0].data_ptr(), self.taps[1].data_ptr()
+        a.gkind, a.n0, a.n1 = spec['gkind'], n0, n1
+        SepPSF.of(spec, dtype, dev).normal(tables=False).attach(self, a)
         a.tau, a.lam = float(tau), float(spec['lam'])
         a.seg_a, a.seg_b = spec['seg']
         a.x, a.xn = self.X[0].data_ptr(), self.X[1].data_ptr()
         a.aux, a.aux_n = self.AUX[0].data_ptr(), self.AUX[1].data_ptr()
-        a.cty = self.cty.data_ptr()
         self.args = a
         if self.lib.pcs_apgd2d_supported(ctypes.byref(a)) != 1:
             raise ValueError('problem not supported by the fused APGD step')
-        self.nblocks = int(self.lib.pcs_apgd2d_nblocks(ctypes.byref(a)))
-        self.partials = torch.empty(4 * self.nblocks, dtype=torch.float64, device=dev)
-        self.ctl = LoopControl(dev)
-        # the reduction counters start at 0 and every launch leaves them at 0
-        self.ws = torch.zeros(int(self.lib.pcs_apgd2d_ws_bytes(ctypes.byref(a))) // 8 + 2, dtype=torch.float64,
-                              device=dev)
-        a.partials, a.ctrl, a.ws = self.partials.data_ptr(), self.ctrl.data_ptr(), self.ws.data_ptr()
-
-    ctrl = property(lambda self: self.ctl.ctrl)
-    hist = property(lambda self: self.ctl.hist)
+        self._init_reduction(a, dev, self.lib.pcs_apgd2d_nblocks, self.lib.pcs_apgd2d_ws_bytes)
 
     def coeffs(self, k0, n, t_old):
         return apgd_coeffs(self.acceleration, self.d, k0, n, t_old)
@@ -340,61 +398,41 @@ class APGD2DEngine:
         return n, self.X[n % 2], self.AUX[n % 2], past_t, h
 
 
-def _common_args(a, spec, dtype, tau, sigma, rho, with_k=True):
-    """The fields pcs_pds2d_args and pcs_pds2d_stencil_args share by name, from a spec and the step
-    sizes (`with_k`: K's kind, edge rule and weights, which only the general-stencil specs carry)."""
-    a.dtype = L.dtype_code(dtype)
-    a.hkind, a.gkind = spec['hkind'], spec['gkind']
-    a.n0, a.n1 = spec['shape']
-    a.tau, a.sigma, a.rho, a.lam = float(tau), float(sigma), float(rho), spec['lam']
-    a.step0, a.step1 = spec['steps']
-    a.seg_a, a.seg_b = spec['seg']
-    if with_k:
-        a.kkind, a.edge = spec['kkind'], int(spec['edge'])
-        a.w0, a.w1 = spec['weights']
-    if isinstance(a, L.PdsArgs):  # one slab, the whole image: no halos
-        a.row0, a.rows = 0, a.n0
-    return a
+def forward_normal(half, dtype):
+    """Whether PDS2DEngine runs a separable PSF of this half width as grad F = N x - Conv^T y (the
+    normal-operator march kernel, pds_nmarch.hpp).  PCS_NMARCH=0: diagnostics, the four-pass march kernel
+    (grad F = Conv^T (Conv x - y))."""
+    return dtype == torch.float32 and half <= 7 and os.environ.get('PCS_NMARCH', '1') != '0'
 
 
-class PDS2DEngine:
+class PDS2DEngine(LoopState):
     """Device state + captured loop for one fused 2-D PDS problem."""
 
     def __init__(self, spec, dtype, tau, sigma, rho, x0, z0, chunk=32, use_graph=True):
         dev = self._init_state(spec, dtype, x0, z0, chunk, use_graph)
-        a = _common_args(L.PdsArgs(), spec, dtype, tau, sigma, rho, with_k=False)
+        a = step_args(spec, dtype, tau, sigma, rho, with_k=False)
         fk = spec['fkind']
-        self.conv = None
         if fk in (L.PCS_F_DENOISE, L.PCS_F_SEPCONV):
             # y = -shift (exact), so x + shift == x - y bit for bit
             self.y = -O.to_dev(spec['shift'], dtype)
             a.y = self.y.data_ptr()
         if fk == L.PCS_F_SEPCONV:
-            conv = spec['conv']
-            sep = conv.separable(rtol=sep_rtol(dtype))
-            if sep is not None:
-                t0, t1, half = sep
-                self.taps = [torch.as_tensor(t0).to(device=dev, dtype=dtype),
-                             torch.as_tensor(t1).to(device=dev, dtype=dtype)]
-                a.taps0, a.taps1 = self.taps[0].data_ptr(), self.taps[1].data_ptr()
-                a.half = half
-                # PCS_NMARCH=0: diagnostics, the four-pass march kernel (grad F = Conv^T (Conv x - y))
-                if dtype == torch.float32 and half <= 7 and os.environ.get('PCS_NMARCH', '1') != '0':
-                    # normal-operator march kernel: grad F = N x - Conv^T y (pds_nmarch.hpp),
-                    # Conv^T y formed once here in fp64
-                    self.ntaps = torch.as_tensor(nmarch_taps(t0, t1, half)).to(dev)
-                    self.cty = conv._adj(-O.to_dev(spec['shift'], torch.float64)).to(dtype).contiguous()
-                    a.cty, a.ntaps = self.cty.data_ptr(), self.ntaps.data_ptr()
+            psf = SepPSF.of(spec, dtype, dev)
+            if psf is not None:
+                if forward_normal(psf.half, dtype):
+                    psf.normal()
+                psf.attach(self, a)
             else:
                 fk = L.PCS_F_GRADBUF
-                self._init_grad_conv(conv, dev)
+                self._init_grad_conv(spec['conv'], dev)
                 a.gbuf = self.Gb.data_ptr()
         a.fkind = fk
         self._init_loop_state(a, fk, self.lib.pcs_pds2d_nblocks, self.lib.pcs_pds2d_ws_bytes, fk != L.PCS_F_GRADBUF)
 
     # ---- the pieces of a constructor (the subclasses' differ in the arguments between them)
     def _init_state(self, spec, dtype, x0, z0, chunk, use_graph, ncomp=2):
-        """The iterate ping-pong buffers (z of `ncomp` components) and the loop's shape; the device."""
+        """The iterate ping-pong buffers (z of `ncomp` components) and the loop's shape; every attribute
+        only some problems fill, at its empty value; the device."""
         self.lib = L.gpu()
         self.spec = spec
         self.dtype = dtype
@@ -405,6 +443,9 @@ class PDS2DEngine:
         self.Z = [z0.to(dtype).clone(), torch.empty(ncomp * self.N, dtype=dtype, device=dev)]
         self.chunk = max(2, chunk + (chunk % 2))
         self.use_graph = use_graph
+        self.conv = self.plans = self.taps = self.cty = self.ntaps = None
+        self.defer = self.nm_fused = False
+        self._fixed_p = 0
         return dev
 
     def _init_grad_conv(self, conv, dev):
@@ -419,59 +460,48 @@ class PDS2DEngine:
         self.Gb = torch.empty(self.N, dtype=self.dtype, device=dev)
 
     def _init_loop_state(self, a, fk, nblocks_fn, ws_bytes_fn, may_run_native):
-        """The step arguments `a` are complete but for what the loop owns: partials, the loop control,
-        the reduction workspace (in-kernel reduce + finalize, one launch per iteration; its counters
-        must start at 0)."""
-        dev = self.X[0].device
+        """The step arguments `a` are complete but for what the loop owns (LoopState._init_reduction:
+        in-kernel reduce + finalize, one launch per iteration)."""
         self.args, self.fkind = a, fk
-        self.nblocks = int(nblocks_fn(ctypes.byref(a)))
-        self._alloc_partials(a, dev)
-        self.ctl = LoopControl(dev)
-        a.ctrl = self.ctrl.data_ptr()
-        self.ws = torch.zeros(int(ws_bytes_fn(ctypes.byref(a))) // 8 + 2, dtype=torch.float64, device=dev)
-        a.ws = self.ws.data_ptr()
+        self._init_reduction(a, self.X[0].device, nblocks_fn, ws_bytes_fn)
         self.graph = None
         # large images: each chunk is launched back to back from C (pcs_pds2d_run) -- per-launch
         # host cost is far below the step, and back-to-back launches measured faster than
         # replaying a captured graph of the same launches; small images keep the graph
         self.native = may_run_native and self.N >= NATIVE_MIN_PIXELS
 
-    ctrl = property(lambda self: self.ctl.ctrl)
-    hist = property(lambda self: self.ctl.hist)
-
     def _alloc_partials(self, a, dev):
         """[nblocks][4] partials; with deferred finalization two such arrays, swapped with the
         iterate parity (the launch of parity p writes array p and finalizes array 1 - p)."""
-        self.defer = DEFER_FIN and isinstance(a, L.PdsArgs)
+        defer = DEFER_FIN and isinstance(a, L.PdsArgs)
         # pcs_pds2d_run may run an iteration as two row-band launches (the band-paired schedule, csrc/pds.hip),
         # which leave the partials of both: run_nblocks is the count its launches write and its flush reduces;
         # the arrays hold the largest count any PCS_RUN_BANDS setting can ask for
         self.run_nblocks = cap = self.nblocks
-        if self.defer:
-            a.x, a.xn = self.X[0].data_ptr(), self.X[1].data_ptr()
-            a.z, a.zn = self.Z[0].data_ptr(), self.Z[1].data_ptr()
-            a.partials = a.x  # placeholder for the planning query (never written)
-            self.run_nblocks = int(self.lib.pcs_pds2d_run_nblocks(ctypes.byref(a), -1))
-            cap = max(cap, self.run_nblocks, int(self.lib.pcs_pds2d_run_nblocks(ctypes.byref(a), 1)))
+        if defer:
+            self._bind(a, 0)  # the iterates only: self.defer is still False
+            self.run_nblocks = int(query(self.lib.pcs_pds2d_run_nblocks, a, -1, partials=a.x))
+            cap = max(cap, self.run_nblocks, int(query(self.lib.pcs_pds2d_run_nblocks, a, 1, partials=a.x)))
         nb4 = cap * 4
-        self.partials = torch.empty((2 if self.defer else 1) * nb4, dtype=torch.float64, device=dev)
-        self.part_halves = [self.partials[:nb4], self.partials[nb4:]] if self.defer else [self.partials]
+        self.partials = torch.empty((2 if defer else 1) * nb4, dtype=torch.float64, device=dev)
+        self.part_halves = [self.partials[:nb4], self.partials[nb4:]] if defer else [self.partials]
         a.partials = self.partials.data_ptr()
-        if self.defer:
+        if defer:
             a.fin_partials = self.part_halves[1].data_ptr()
+        self.defer = defer
 
     def _bind(self, a, p):
         """Point the step's iterate buffers at parity p (reads buffers p, writes 1 - p)."""
         a.x, a.xn = self.X[p].data_ptr(), self.X[1 - p].data_ptr()
         a.z, a.zn = self.Z[p].data_ptr(), self.Z[1 - p].data_ptr()
-        if getattr(self, 'defer', False):
+        if self.defer:
             a.partials, a.fin_partials = self.part_halves[p].data_ptr(), self.part_halves[1 - p].data_ptr()
 
     def _flush(self, next_p, hist, run=False):
         """Deferred finalization: finalize the last launch's partials (parity 1 - next_p) if they
         are pending (pcs_pds_finalize_pending; a no-op when the loop has stopped).  `run`: the last
         iteration came from pcs_pds2d_run (its partials count), not from a single step."""
-        if getattr(self, 'defer', False):
+        if self.defer:
             L.check(self.lib.pcs_pds_finalize_pending(L.ptr(self.part_halves[1 - next_p]),
                                                       self.run_nblocks if run else self.nblocks,
                                                       L.ptr(self.ctrl), L.ptr(hist), L.stream()),
@@ -554,7 +584,7 @@ class PDS2DEngine:
         parity the previous call left (odd counts allowed): native images as one
         pcs_pds2d_run of n launches, graph images as whole captured chunks while the parity
         allows plus eager single iterations."""
-        p = getattr(self, '_fixed_p', 0)
+        p = self._fixed_p
         if self.native:
             a = self.args
             self._bind(a, p)
@@ -638,6 +668,42 @@ class PDS2DEngine:
         return n, self.X[n % 2], self.Z[n % 2], ctl.rows(n)
 
 
+Route = collections.namedtuple('Route', 'march fkind nm_fused drop')
+
+
+def stencil_march_on():
+    """PCS_STENCIL_MARCH=0: the general-stencil engine always runs the tile kernel."""
+    return os.environ.get('PCS_STENCIL_MARCH', '1') != '0'
+
+
+def nm_fused_route(lib, a, **fields):
+    """Whether the library runs the step `a` (separable operands and N tables set) as the fused
+    normal-operator march: one launch (pds_nmarch.hpp for backward / centred K in fp32, pds_nm64.hip for
+    every Gradient K in fp64) that reads no gradient buffer -- asked with none."""
+    return query(lib.pcs_pds2d_path, a, gbuf=None, **fields) in L.PCS_PATH_FUSED_NORMAL
+
+
+def route_stencil2d(lib, a):
+    """Where a general-stencil problem runs.  `a`: its pcs_pds2d_args with every candidate pointer set --
+    the iterates, partials, y or the gradient buffer, and for a separable PSF fkind SEPCONV with taps, cty
+    and ntaps beside the gradient buffer.  Route(march, fkind, nm_fused, drop): `march` False is the tile
+    kernel (pcs_pds2d_stencil_step, on the spec's own fkind); otherwise pcs_pds2d_step takes `a` with
+    `fkind` and the optional pointers named in `drop` cleared.  A separable PSF runs, in this order of
+    preference, as the fused normal-operator march (`nm_fused`), as the two-launch form (N x by the
+    in-plane normal-operator kernel into the gradient buffer, then the march step: no ntaps), or like any
+    other PSF through the correlation passes (GRADBUF: no cty either)."""
+    fk, nm_fused, drop = a.fkind, False, ()
+    if not stencil_march_on():
+        return Route(False, fk, False, drop)
+    if fk == L.PCS_F_SEPCONV:
+        nm_fused = nm_fused_route(lib, a)
+        drop = () if nm_fused else ('ntaps',)
+        if query(lib.pcs_pds2d_supported, a, **dict.fromkeys(drop)) != 1:
+            fk, nm_fused, drop = L.PCS_F_GRADBUF, False, ('cty', 'ntaps')
+    march = query(lib.pcs_pds2d_supported, a, fkind=fk, **dict.fromkeys(drop)) == 1
+    return Route(march, fk, nm_fused, drop)
+
+
 class PDS2DStencilEngine(PDS2DEngine):
     """Device state + loop of the general-stencil fused step (pcs_pds2d_stencil_step): the same
     loop machinery as PDS2DEngine (device stop flag, chunks launched from C for large images,
@@ -646,7 +712,6 @@ class PDS2DStencilEngine(PDS2DEngine):
     def __init__(self, spec, dtype, tau, sigma, rho, x0, z0, chunk=32, use_graph=True):
         dev = self._init_state(spec, dtype, x0, z0, chunk, use_graph, spec['ncomp'])
         fk = spec['fkind']
-        self.conv = None
         if fk in (L.PCS_F_DENOISE, L.PCS_F_GRADBUF):
             self.y = -O.to_dev(spec['shift'], dtype)  # y = -shift exactly
         if fk == L.PCS_F_GRADBUF:
@@ -654,53 +719,27 @@ class PDS2DStencilEngine(PDS2DEngine):
         gsrc = None if fk == L.PCS_F_NULL else (self.Gb if fk == L.PCS_F_GRADBUF else self.y)
         # images the general-stencil row-marching kernel covers (pds_smarch.hpp: 64-column strips,
         # 4-column groups; fp32 and fp64, every K kind in fp64) run through pcs_pds2d_step with K in
-        # the args; the rest through the tile kernel (pcs_pds2d_stencil_step).  PCS_STENCIL_MARCH=0:
-        # always the tile kernel.
-        self.march = False
-        a = None
-        f64 = dtype == torch.float64
-        if dtype in (torch.float32, torch.float64) and os.environ.get('PCS_STENCIL_MARCH', '1') != '0':
-            a = _common_args(L.PdsArgs(), spec, dtype, tau, sigma, rho)
+        # the args; the rest through the tile kernel (pcs_pds2d_stencil_step): route_stencil2d decides
+        # on the march's candidate arguments
+        a = step_args(spec, dtype, tau, sigma, rho)
+        a.fkind = fk
+        self._bind(a, 0)
+        a.partials = a.x  # stands in until the loop state exists (query())
+        if fk == L.PCS_F_DENOISE:
+            a.y = gsrc.data_ptr()
+        elif fk == L.PCS_F_GRADBUF:
+            a.gbuf = gsrc.data_ptr()
+            psf = SepPSF.of(spec, dtype, dev, max_half=7) if stencil_march_on() else None
+            if psf is not None:
+                psf.normal().attach(self, a)
+                a.fkind, a.y = L.PCS_F_SEPCONV, self.y.data_ptr()
+        self.march, fk, self.nm_fused, drop = route_stencil2d(self.lib, a)
+        if self.march:
             a.fkind = fk
-            self._bind(a, 0)
-            a.partials = a.x  # placeholder for the support query (never written)
-            if fk == L.PCS_F_DENOISE:
-                a.y = gsrc.data_ptr()
-            elif fk == L.PCS_F_GRADBUF:
-                a.gbuf = gsrc.data_ptr()
-                # separable PSF: grad F = N x - Conv^T y (the in-plane normal-operator kernel into the
-                # gradient buffer, then the march step), Conv^T y formed once here in fp64
-                sep = self.conv.separable(rtol=sep_rtol(dtype))
-                if sep is not None and sep[2] <= 7:
-                    t0, t1, half = sep
-                    self.taps = [torch.as_tensor(t).to(device=dev, dtype=dtype) for t in (t0, t1)]
-                    self.cty = self.conv._adj(-O.to_dev(spec['shift'], torch.float64)).to(dtype).contiguous()
-                    a.fkind, a.half, a.y = L.PCS_F_SEPCONV, half, self.y.data_ptr()
-                    a.taps0, a.taps1 = self.taps[0].data_ptr(), self.taps[1].data_ptr()
-                    a.cty = self.cty.data_ptr()
-                    # the N tables: the fused normal-operator march (one launch: pds_nmarch.hpp for
-                    # backward / centred K in fp32, pds_nm64.hip for every Gradient K in fp64) when the
-                    # library takes the problem -- supported with no gradient buffer; otherwise the
-                    # two-launch form (N x by the in-plane normal-operator kernel, then the march step)
-                    self.ntaps = torch.as_tensor(nmarch_taps(t0, t1, half, np.float64 if f64 else np.float32)).to(dev)
-                    a.ntaps = self.ntaps.data_ptr()
-                    a.gbuf = None
-                    self.nm_fused = self.lib.pcs_pds2d_path(ctypes.byref(a)) in L.PCS_PATH_FUSED_NORMAL
-                    if not self.nm_fused:
-                        a.ntaps = None
-                    a.gbuf = gsrc.data_ptr()
-                    if self.lib.pcs_pds2d_supported(ctypes.byref(a)) != 1:
-                        a.fkind, a.cty, a.ntaps = fk, None, None
-                        self.nm_fused = False
-                    else:
-                        fk = L.PCS_F_SEPCONV
-            if self.lib.pcs_pds2d_supported(ctypes.byref(a)) == 1:
-                self.march = True
-            else:
-                a = None
-                fk = spec['fkind']
-        if a is None:
-            a = _common_args(L.StencilArgs(), spec, dtype, tau, sigma, rho)
+            for name in drop:
+                setattr(a, name, None)
+        else:
+            a = step_args(spec, dtype, tau, sigma, rho, cls=L.StencilArgs)
             a.fkind = fk
             if gsrc is not None:
                 a.g = gsrc.data_ptr()
@@ -714,7 +753,7 @@ class PDS2DStencilEngine(PDS2DEngine):
         march (one launch, `nm_fused`) or one pcs_pds2d_step call holding two launches (N x into the
         gradient buffer, the step), timed as 'step' together and 'conv_nx' alone."""
         res = PDS2DEngine.time_iteration_kernels(self, n)
-        if self.fkind == L.PCS_F_SEPCONV and not getattr(self, 'nm_fused', False):
+        if self.fkind == L.PCS_F_SEPCONV and not self.nm_fused:
             a, lib = self.args, self.lib
             timed = LaunchTimer()
             for i in range(min(n, 50)):
@@ -796,11 +835,11 @@ class PDS2DMaskEngine(PDS2DEngine):
         self.ZM[0][self.idx] = z0[:m].to(dtype)
         self.ym = torch.full((N,), float('nan'), dtype=dtype, device=dev)
         self.ym[self.idx] = -O.to_dev(spec['mask_shift'], dtype)  # y = -shift, exactly
-        a = _common_args(L.PdsArgs(), spec, dtype, tau, sigma, rho)
+        a = step_args(spec, dtype, tau, sigma, rho)
         a.fkind = L.PCS_F_NULL
         a.mkind, a.ym = L.PCS_M_L1LOSS, self.ym.data_ptr()
         self._bind(a, 0)
-        a.partials = a.x  # placeholder for the support query (never written)
+        a.partials = a.x  # stands in until the loop state exists (query())
         if self.lib.pcs_pds2d_supported(ctypes.byref(a)) != 1:
             raise ValueError('masked data-fidelity problem not supported by the fused step')
         self._init_loop_state(a, L.PCS_F_NULL, self.lib.pcs_pds2d_nblocks, self.lib.pcs_pds2d_ws_bytes, True)

@@ -32,16 +32,12 @@ import torch
 
 from .. import _lib as L
 from .. import _ops as O
-from ..core.functional import ProxFuncPostComp
 from ..core.linop import LinOpComp
-from ..core.map import DiffMapComp
-from ..func.base import IndicatorFunctional, NullDifferentiableFunctional, NullProximableFunctional
-from ..func.penalty import L1Norm, L21Norm
 from ..linop.conv import Convolve1DOp
 from ..linop.diff import GradientOp
 from ..parallel.slab import SlabLayout
-from ._loop import LaunchTimer, LoopControl, capture_agreed
-from .engine import _half_loss_data
+from ._loop import LaunchTimer, LoopState, capture_agreed, worst_over_ranks
+from .engine import fused_spec, match_f, match_g, match_h, query
 
 
 def conv_chain(C, shape):
@@ -58,50 +54,17 @@ def match_pds3d(F, G, H, K, has_H):
     """Engine spec dict if (F, G, H, K) is a fused 3-D problem, else None."""
     if not has_H or not isinstance(K, GradientOp) or len(K.dims) != 3:
         return None
-    kinds = {'forward': L.PCS_FORWARD, 'backward': L.PCS_BACKWARD, 'centered': L.PCS_CENTERED}
-    if K.kind not in kinds:
+    if K.kind not in L.KINDS:
         return None
     shape = tuple(K.dims)
     N = int(np.prod(shape))
     # kkind: forward -> k_pds3d; backward / centred (the reference's default) -> k_pds3d_gen
-    spec = {'ndim': 3, 'shape': shape, 'steps': tuple(K.steps), 'kkind': kinds[K.kind], 'edge': int(K.edge)}
-    base, lam = H, 1.0
-    if isinstance(H, ProxFuncPostComp):
-        if H.shift != 0:
-            return None
-        base, lam = H.prox_func, float(H.scale)
-    if isinstance(base, L21Norm) and base.pixel_d == 3 and base.dim == 3 * N:
-        spec['hkind'] = L.PCS_H_L21
-    elif isinstance(base, L1Norm) and base.dim == 3 * N:
-        spec['hkind'] = L.PCS_H_L1
-    else:
-        return None
-    spec['lam'] = lam
-    if G is None or isinstance(G, NullProximableFunctional):
-        spec['gkind'], spec['seg'] = L.PCS_G_NULL, (0.0, 1.0)
-    elif isinstance(G, IndicatorFunctional) and G.kind == 'nonneg':
-        spec['gkind'], spec['seg'] = L.PCS_G_NONNEG, (0.0, 1.0)
-    elif isinstance(G, IndicatorFunctional) and G.kind == 'segment':
-        spec['gkind'], spec['seg'] = L.PCS_G_SEGMENT, G.params
-    else:
-        return None
-    if F is None or isinstance(F, NullDifferentiableFunctional):
-        spec['fkind'] = L.PCS_F_NULL
-        return spec
-    s = _half_loss_data(F)
-    if s is not None and O.numel(s) == N:
-        spec['fkind'], spec['shift'] = L.PCS_F_DENOISE, s
-        return spec
-    if isinstance(F, DiffMapComp):
-        chain = conv_chain(F.map2, shape)
-        s = _half_loss_data(F.map1)
-        if chain and s is not None and O.numel(s) == N:
-            spec['fkind'], spec['shift'], spec['chain'] = L.PCS_F_GRADBUF, s, chain
-            return spec
-    return None
+    head = {'ndim': 3, 'shape': shape, 'steps': tuple(K.steps), 'kkind': L.KINDS[K.kind], 'edge': int(K.edge)}
+    return fused_spec(head, match_h(H, 3, N), match_g(G),
+                      match_f(F, N, lambda op: conv_chain(op, shape), L.PCS_F_GRADBUF, 'chain'))
 
 
-class PDS3DEngine:
+class PDS3DEngine(LoopState):
     """Device state + loop of one rank's slab (the whole volume when world == 1)."""
 
     def __init__(self, spec, dtype, tau, sigma, rho, x0, z0, comm=None, rank=0, world=1, chunk=8, use_graph=True,
@@ -128,6 +91,7 @@ class PDS3DEngine:
         self.fkind = fk
         dev = torch.device('cuda', torch.cuda.current_device())
         self.chain = []
+        self.fused0 = self.sep2 = None  # set with a convolution chain only
         self.ata = False
         reach = 0
         if fk == L.PCS_F_GRADBUF:
@@ -184,9 +148,7 @@ class PDS3DEngine:
                 # one-task-per-workgroup grid (round 4: 5.6 against 7.2 ms for the two passes at
                 # 1024^3), fp64 (C5 39.0 against 36.7-36.9 it/s with the three-pass chain,
                 # profiles/r4_c5_ata_ab2.txt).  PCS_3D_ATA=0/1 overrides
-                self.ata = False
-                ata_default = '1'
-                if self.sep2 and os.environ.get('PCS_3D_ATA', ata_default) == '1':
+                if self.sep2 and os.environ.get('PCS_3D_ATA', '1') == '1':
                     (ha, ka, oa), (hb, kb, ob) = self._inplane_ab(False)
                     rc = self.lib.pcs_conv2d_sep_ata_planes(L.dtcode(self.T[0]), L.ptr(self.T[0]), L.ptr(self.T[1]),
                                                             0, n1, n2, L.ptr(ha), ka, oa, L.ptr(hb), kb, ob,
@@ -204,7 +166,9 @@ class PDS3DEngine:
         # Needs the fused axis-0 gradient with both in-plane passes in one launch (C4/C5).
         self.band = hx + 1
         self.banded = (fk == L.PCS_F_GRADBUF and self.fused0 and self.sep2 and world > 1
-                       and self.rows > 2 * self.band) if fk == L.PCS_F_GRADBUF else False
+                       and self.rows > 2 * self.band)
+        self.nb_bands = None
+        self._pending_ex = self._pending_ag = None
         self.overlap = bool(overlap)
         # banded order: 'split' = g of the boundary bands before the exchange starts, the
         # interior's g after (the exchange overlaps the interior g + update); 'fullg' = g on
@@ -233,14 +197,6 @@ class PDS3DEngine:
             a.g = self.yw.data_ptr()
         elif fk == L.PCS_F_GRADBUF:
             a.g = self.gbuf.data_ptr()
-        self.nblocks = int(self.lib.pcs_pds3d_nblocks(ctypes.byref(a)))
-        self.partials = torch.empty(self.nblocks * 4, dtype=torch.float64, device=dev)
-        a.partials = self.partials.data_ptr()
-        self.ctl = LoopControl(dev)
-        a.ctrl = self.ctrl.data_ptr()
-        self.ws = torch.zeros(int(self.lib.pcs_pds3d_ws_bytes(ctypes.byref(a))) // 8 + 2, dtype=torch.float64,
-                              device=dev)
-        a.ws = self.ws.data_ptr()
         self.base_args = a
         if self.ata:  # C12^T y on every stored plane (setup, once)
             self.yb = torch.empty_like(self.yw)
@@ -255,23 +211,16 @@ class PDS3DEngine:
         self.fold = False
         if self.ata and self.kkind == L.PCS_FORWARD and os.environ.get('PCS_3D_FOLD', '1') != '0':
             _, h0, _, k0, off0 = self.ax0
-            b = L.Pds3Args()
-            ctypes.pointer(b)[0] = a
-            b.fkind, b.g, b.conv0_w, b.conv0_taps, b.conv0_k, b.conv0_off = (L.PCS_F_CONV0, self.T[0].data_ptr(),
-                                                                            self.yb.data_ptr(), h0.data_ptr(),
-                                                                            int(k0), int(off0))
-            b.x = b.xn = b.z = b.zn = self.X[0].data_ptr()  # placeholders: the query launches nothing
-            if int(self.lib.pcs_pds3d_nblocks_bands(ctypes.byref(b), 0, self.rows, self.rows, self.rows)) > 0:
-                a.fkind, a.g, a.conv0_w, a.conv0_taps, a.conv0_k, a.conv0_off = (b.fkind, b.g, b.conv0_w,
-                                                                                 b.conv0_taps, b.conv0_k, b.conv0_off)
+            folded = dict(fkind=L.PCS_F_CONV0, g=self.T[0].data_ptr(), conv0_w=self.yb.data_ptr(),
+                          conv0_taps=h0.data_ptr(), conv0_k=int(k0), conv0_off=int(off0))
+            ph = self.X[0].data_ptr()  # the iterates are bound per parity later, the partials allocated below
+            if int(query(self.lib.pcs_pds3d_nblocks_bands, a, 0, self.rows, self.rows, self.rows, x=ph, xn=ph, z=ph,
+                         zn=ph, partials=ph, **folded)) > 0:
+                for name, v in folded.items():
+                    setattr(a, name, v)
                 self.fold = True
-                # the per-workgroup partials and the reduction workspace follow the folded launch's grid
-                self.nblocks = int(self.lib.pcs_pds3d_nblocks(ctypes.byref(a)))
-                self.partials = torch.empty(self.nblocks * 4, dtype=torch.float64, device=dev)
-                a.partials = self.partials.data_ptr()
-                self.ws = torch.zeros(int(self.lib.pcs_pds3d_ws_bytes(ctypes.byref(a))) // 8 + 2, dtype=torch.float64,
-                                      device=dev)
-                a.ws = self.ws.data_ptr()
+        # the per-workgroup partials and the reduction workspace follow the launch's grid: the folded one's
+        self._init_reduction(a, dev, self.lib.pcs_pds3d_nblocks, self.lib.pcs_pds3d_ws_bytes)
         self.args = [self._args_for(p) for p in (0, 1)]
         self.sums = torch.zeros(4, dtype=torch.float64, device=dev)
         self.gathered = torch.zeros(4 * world, dtype=torch.float64, device=dev)
@@ -290,9 +239,6 @@ class PDS3DEngine:
         self.chunk = max(2, chunk + chunk % 2)
         # graphs: one GPU, or the native RCCL transport (PCS_3D_GRAPH=0 launches eagerly)
         self.use_graph = use_graph and (world == 1 or (self.native_comm and os.environ.get('PCS_3D_GRAPH', '1') != '0'))
-
-    ctrl = property(lambda self: self.ctl.ctrl)
-    hist = property(lambda self: self.ctl.hist)
 
     def _args_for(self, p):
         b = L.Pds3Args()
@@ -436,7 +382,7 @@ class PDS3DEngine:
                 'pcs_reduce_partials')
 
     def _init_bands(self):
-        if getattr(self, 'nb_bands', None) is not None:
+        if self.nb_bands is not None:
             return
         R, B = self.rows, self.band
         a = self.args[0]
@@ -524,7 +470,7 @@ class PDS3DEngine:
     def _drain(self):
         """Order the current stream after the in-flight exchange / all-gather and run the loop
         control of the iteration they belong to."""
-        ex, ag = getattr(self, '_pending_ex', None), getattr(self, '_pending_ag', None)
+        ex, ag = self._pending_ex, self._pending_ag
         self._pending_ex = self._pending_ag = None
         if ex is not None:
             ex.wait()
@@ -604,12 +550,8 @@ class PDS3DEngine:
             e1.record()
             torch.cuda.synchronize()
             times.append(e0.elapsed_time(e1))
-        dev = self.sums.device
-        mine = torch.tensor(times + [0.0], dtype=torch.float64, device=dev)
-        allt = torch.zeros(4 * self.world, dtype=torch.float64, device=dev)
-        self.comm.allgather(mine, allt)
-        worst = allt.view(self.world, 4).max(dim=0).values[:3]
-        best = int(torch.argmin(worst).item())
+        worst = worst_over_ranks(self.comm, times, self.world, self.sums.device)
+        best = worst.index(min(worst))
         self.overlap = cands[best] != 'serial'
         if self.overlap:
             self.order = cands[best]

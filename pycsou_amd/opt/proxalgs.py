@@ -27,6 +27,7 @@ from ..core.map import DifferentiableMap
 from ..core.solver import GenericIterativeAlgorithm
 from ..func.base import NullDifferentiableFunctional, NullProximableFunctional
 from ..linop.base import IdentityOperator, NullOperator
+from ._loop import LoopControl, LoopViews
 
 
 def _frame(columns, rows):
@@ -70,7 +71,7 @@ def _rel_improvement(old, new):
     return float(np.sqrt(d2) / np.sqrt(n2))
 
 
-class _DeviceLoop:
+class _DeviceLoop(LoopViews):
     """Loop control of the per-operator (generic) path on the device: after each iteration the
     relative-improvement sums are reduced on the GPU (pcs_rel_sums) and pcs_pds_finalize
     records the diagnostics row and the reference loop condition (solver.py:65-66,
@@ -81,7 +82,6 @@ class _DeviceLoop:
 
     def __init__(self, max_iter, min_iter, thr, has_dual, device, lag=3, cap=None):
         from .. import _lib as L
-        from ._loop import LoopControl
         self.L, self.lib = L, L.gpu()
         self.ctl = LoopControl(device)
         # cap: every history row up front (the graph chunks cannot grow it)
@@ -89,9 +89,6 @@ class _DeviceLoop:
         self.sums = torch.zeros(4, dtype=torch.float64, device=device)
         self.has_dual, self.lag = has_dual, lag
         self.issued = 0
-
-    ctrl = property(lambda self: self.ctl.ctrl)
-    hist = property(lambda self: self.ctl.hist)
 
     def record(self, x_old, x, z_old=None, z=None):
         """Enqueue this iteration's sums + finalize and an async read-back of the control."""

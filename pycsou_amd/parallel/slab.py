@@ -37,8 +37,8 @@ import torch
 import torch.distributed as dist
 
 from .. import _lib as L
-from ..opt._loop import LaunchTimer, LoopControl, capture_agreed
-from ..opt.engine import nmarch_taps
+from ..opt._loop import LaunchTimer, LoopControl, LoopViews, capture_agreed, worst_over_ranks
+from ..opt.engine import SepPSF, nm_fused_route, step_args
 from .. import _ops as O
 
 
@@ -301,7 +301,7 @@ class SlabLayout:
         return pairs
 
 
-class SlabPDS2D:
+class SlabPDS2D(LoopViews):
     """One rank's slab of a fused 2-D PDS problem.
 
     ``spec`` is the global problem's engine spec (``PDS._fused_spec()``: shape, H/G kinds,
@@ -323,31 +323,20 @@ class SlabPDS2D:
         kk = spec.get('kkind', L.PCS_K_GRAD_FORWARD)
         nc = spec.get('ncomp', 2)
         self.ncomp = nc
-        a = L.PdsArgs()
-        a.dtype = L.dtype_code(dtype)
-        a.hkind, a.gkind = spec['hkind'], spec['gkind']
-        a.n0, a.n1, a.row0, a.rows = n0, n1, self.row0, self.rows
-        a.tau, a.sigma, a.rho, a.lam = float(tau), float(sigma), float(rho), spec['lam']
-        a.step0, a.step1 = spec['steps']
-        a.seg_a, a.seg_b = spec['seg']
-        a.kkind, a.edge = kk, int(spec.get('edge', True))
-        a.w0, a.w1 = spec.get('weights', (1.0, 1.0))
+        a = step_args(spec, dtype, tau, sigma, rho, lay=lay)
         dev = torch.device('cuda', torch.cuda.current_device())
         fwd = kk == L.PCS_K_GRAD_FORWARD
         half, mode = 0, 'pointwise'
         conv = spec.get('conv')
+        psf = self.taps = self.cty = self.ntaps = None
         if fk in (L.PCS_F_SEPCONV, L.PCS_F_GRADBUF) and conv is not None:
-            sep = conv.separable(rtol=2e-7 if dtype == torch.float32 else 1e-13)
-            if sep is not None and (fwd or sep[2] <= 7):
+            psf = SepPSF.of(spec, dtype, dev, max_half=None if fwd else 7)
+            if psf is not None:
                 # forward K: the (normal-operator) march kernels; other K: the fused normal-operator
                 # march (fp32 pds_nmarch.hpp, fp64 pds_nm64.hip) or N x by the in-plane normal-operator
                 # pass into a buffer, then the general-stencil march step
                 mode = 'sep' if fwd else 'sep_normal'
-                t0, t1, half = sep
-                self.taps = [torch.as_tensor(t0).to(device=dev, dtype=dtype),
-                             torch.as_tensor(t1).to(device=dev, dtype=dtype)]
-                a.taps0, a.taps1 = self.taps[0].data_ptr(), self.taps[1].data_ptr()
-                a.half = half
+                half = psf.half
                 fk = L.PCS_F_SEPCONV
             else:
                 # general (non-separable) PSF: grad F = Conv^T (Conv x - y) by two packed-plan
@@ -410,29 +399,20 @@ class SlabPDS2D:
         if mode == 'conv2d':
             self.R = torch.zeros_like(self.X[0])
             a.rbuf = self.R.data_ptr()
-        f64 = dtype == torch.float64
+        self.nm_fused = False
         if mode == 'sep_normal' or (mode == 'sep' and half <= 7 and os.environ.get('PCS_NMARCH', '1') != '0'):
             # Conv^T y in fp64 on this rank's window only (own rows + the y halo), from the y rows
             # within the PSF's reach of it -- exact, since the sub-image's zero boundary falls where
-            # the image's does or beyond the reach
-            if half <= 7:
-                # 'sep_normal' too: backward / centred K run the fused normal-operator march when the
-                # library takes it (no N x pass, no gradient buffer read); fp64 every Gradient K
-                # (pds_nm64.hip, its N tables in fp64)
-                self.ntaps = torch.as_tensor(nmarch_taps(t0, t1, half, np.float64 if f64 else np.float32)).to(dev)
-                a.ntaps = self.ntaps.data_ptr()
-            self.cty = self._padded(self._cty_window(spec, hy).to(dtype).contiguous())
-            a.cty = self.cty.data_ptr()
-        self.nm_fused = False
-        if mode in ('sep_normal', 'sep') and getattr(self, 'ntaps', None) is not None:
-            # the fused normal-operator march (one launch, no gradient buffer) when the library runs it
-            # for these arguments (the iterate pointers are bound per parity later: placeholders for the
-            # query, never written)
-            saved = (a.gbuf, a.x, a.xn, a.z, a.zn, a.partials)
+            # the image's does or beyond the reach.  'sep_normal' too: backward / centred K run the fused
+            # normal-operator march when the library takes it (no N x pass, no gradient buffer read)
+            psf.normal(self._cty_window(spec, hy))
+            psf.cty = self._padded(psf.cty)
+        if psf is not None:
+            psf.attach(self, a)
+        if psf is not None and psf.ntaps is not None:
+            # the iterate pointers are bound per parity later and the partials allocated below
             ph = self.X[0].data_ptr()
-            a.gbuf, a.x, a.xn, a.z, a.zn, a.partials = None, ph, ph, ph, ph, ph
-            self.nm_fused = self.lib.pcs_pds2d_path(ctypes.byref(a)) in L.PCS_PATH_FUSED_NORMAL
-            a.gbuf, a.x, a.xn, a.z, a.zn, a.partials = saved
+            self.nm_fused = nm_fused_route(self.lib, a, x=ph, xn=ph, z=ph, zn=ph, partials=ph)
         self.nblocks = int(self.lib.pcs_pds2d_nblocks(ctypes.byref(a)))
         if self.nblocks < 0:
             kname = {L.PCS_K_GRAD_FORWARD: 'forward Gradient', L.PCS_K_GRAD_BACKWARD: 'backward Gradient',
@@ -465,6 +445,7 @@ class SlabPDS2D:
         if self.depth > 1 and not self.native:
             raise ValueError('deep halos run in the native loop only (pcs_slab2d_deep_run): an RCCL process group')
         self._deep = None
+        self._tuned = False
         self._b = 0
         # the gradient passes of 'conv2d' / 'sep_normal' run once per iteration over the whole slab:
         # no banded (overlapped) schedule for them
@@ -477,9 +458,6 @@ class SlabPDS2D:
         gc = int(os.environ.get('PCS_SLAB_GRAPH', '32' if world > 1 else '0') or 0)
         self.graph_chunk = (gc + gc % 2) if self.native and gc > 0 else 0
         self._graph = None
-
-    ctrl = property(lambda self: self.ctl.ctrl)
-    hist = property(lambda self: self.ctl.hist)
 
     def _padded(self, t):
         """t inside a buffer with self.pad zero rows before and after it (the view keeps the storage alive);
@@ -590,7 +568,7 @@ class SlabPDS2D:
             torch.cuda.synchronize()
             L.load().pcs_slab2d_destroy(self._plan)
             self._plan = None
-        if getattr(self, '_deep', None) is not None:
+        if self._deep is not None:
             torch.cuda.synchronize()
             L.load().pcs_slab2d_deep_destroy(self._deep)
             self._deep = None
@@ -665,7 +643,7 @@ class SlabPDS2D:
                 self._b = (self._b + int(k)) % self.nbuf
             return
         if self.native:
-            if (not getattr(self, '_tuned', False) and self.world > 1 and self.overlap and k >= 8
+            if (not self._tuned and self.world > 1 and self.overlap and k >= 8
                     and getattr(self.comm, 'tunable', False)):
                 k -= self._autotune()
             if self.graph_chunk and k >= self.graph_chunk:
@@ -719,13 +697,9 @@ class SlabPDS2D:
             torch.cuda.synchronize()
             self._p ^= 1
             times.append(e0.elapsed_time(e1) / 3)
-        dev = self.sums.device
-        mine = torch.tensor(times + [0.0, 0.0], dtype=torch.float64, device=dev)
-        allt = torch.zeros(4 * self.world, dtype=torch.float64, device=dev)
-        self.comm.allgather(mine, allt)
-        worst = allt.view(self.world, 4).max(dim=0).values
-        self.overlap = float(worst[1]) < float(worst[0])
-        self.tune_ms = [float(worst[0]), float(worst[1])]
+        worst = worst_over_ranks(self.comm, times, self.world, self.sums.device)
+        self.overlap = worst[1] < worst[0]
+        self.tune_ms = worst
         self._native_plan()
         self._tuned = True
         return 8
@@ -804,11 +778,7 @@ def comm_probe(eng, reps=5):
         e1.record()
         torch.cuda.synchronize()
         out.append(e0.elapsed_time(e1) / reps)
-    dev = eng.sums.device
-    mine = torch.tensor(out + [0.0], dtype=torch.float64, device=dev)
-    allt = torch.zeros(4 * eng.world, dtype=torch.float64, device=dev)
-    comm.allgather(mine, allt)
-    worst = allt.view(eng.world, 4).max(dim=0).values[:3].tolist()
+    worst = worst_over_ranks(comm, out, eng.world, eng.sums.device)
     res = {k: round(v, 4) for k, v in zip(phases, worst)}
     res['halo_bytes_per_side'] = halo
     res['exchange_GBps_per_side'] = round(halo / (res['exchange_ms'] * 1e-3) / 1e9, 2) if res['exchange_ms'] > 0 else None
