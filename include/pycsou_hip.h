@@ -14,6 +14,14 @@
  *    all of them are hipGraph-capturable on `stream`.
  *  - Workspaces (`ws`) are caller-allocated device buffers of the size the
  *    matching *_ws_bytes() query returns.
+ *  - Caller-owned scratch (ws, partials, the control block, the history): the
+ *    advertised size is all a call touches -- nothing is read or written past
+ *    it -- and every such argument says what its contents on entry mean:
+ *    "contents on entry: arbitrary" (every slot a call reads it has written
+ *    first; the buffer may be shared by successive calls on one stream) or
+ *    "zeroed once before first use" (the call keeps counters there and leaves
+ *    them at zero).  Contents on return are unspecified unless stated.
+ *    INTEGRATION.md lists every such buffer with size, alignment and contents.
  *
  * Each entry point names the reference interface it replaces (file:line in
  * dhamm97/pycsou; PyLops 1.x for the operators pycsou delegates to it).
@@ -103,8 +111,8 @@ int pcs_dirderiv_adj(int dtype, const void* y, const void* v, int v_is_field, vo
  * PCS_CUMSUM_SPAN_STRIDED (inner > 1) samples and handled reduce-then-scan in three launches (segment
  * totals into ws, a scan of the totals, the offset scan); no workgroup ever waits for another.  ws then
  * holds pcs_cumsum_ws_bytes(ndim, dims, axis) bytes, 8-byte aligned (the function returns 0 when no
- * workspace is needed, -1 on bad arguments, and never decreases in the axis length; it stays below
- * PCS_CUMSUM_WS_MAX for any shape).  x == out is allowed: every sample is read and written by the same
+ * workspace is needed -- ws may then be NULL --, -1 on bad arguments, and never decreases in the axis
+ * length; it stays below PCS_CUMSUM_WS_MAX for any shape; contents on entry: arbitrary).  x == out is allowed: every sample is read and written by the same
  * thread.  A negative dim is PCS_EINVAL, a zero dim an empty array (0, no launch). */
 #define PCS_CUMSUM_SPAN 2048
 #define PCS_CUMSUM_SPAN_STRIDED 64
@@ -208,8 +216,8 @@ int pcs_gather_or_zero(int dtype, const void* y, const int32_t* inv, void* out, 
  *  - Every longer row is cut by the caller into chunks of PCS_SPMV_CHUNK entries (the last one shorter), listed
  *    row by row: chunk c covers entries chunk_start[c] .. of row chunk_row[c]; long row i is long_row[i] and
  *    owns chunks long_first[i] .. long_first[i + 1] - 1 (long_first has nlong + 1 entries, all four lists are
- *    int64 device arrays).  One workgroup sums one chunk into partials[c] (nchunks doubles, 8-byte aligned),
- *    then one thread per long row adds its partials in chunk order.  A row of more than PCS_SPMV_LONG_ROW
+ *    int64 device arrays).  One workgroup sums one chunk into partials[c] (nchunks doubles, 8-byte aligned,
+ *    contents on entry: arbitrary), then one thread per long row adds its partials in chunk order.  A row of more than PCS_SPMV_LONG_ROW
  *    entries that is not listed is left unwritten.
  * Sums are carried in fp64 and rounded once.  The order of every sum depends on (rowptr, lanes) alone, so two
  * calls return the same bits; there are no atomics.  Empty matrices and empty rows are legal (an empty row
@@ -230,7 +238,8 @@ int pcs_csr_spmv(int dtype, int64_t nrows, int64_t ncols, int64_t nnz, const int
  *   axis 0:  out (nrows x nb) = A X,    X (ncols x nb): min(64, nb rounded up to a power of two) lanes across the columns of one row,
  *            each walking the row's entries in order (rows of any length; the chunk lists are not used).
  *   axis 1:  out (nb x nrows) = X A^T,  X (nb x ncols): the kernels of pcs_csr_spmv with the batch on grid y;
- *            partials holds nb * nchunks doubles (partials_len >= that), batch row b the bits of pcs_csr_spmv.
+ *            partials holds nb * nchunks doubles (partials_len >= that; 8-byte aligned, contents on entry:
+ *            arbitrary), batch row b the bits of pcs_csr_spmv.  Axis 0 with nb > 1 does not touch partials.
  *   nb == 1: either axis is that vector product, bit for bit pcs_csr_spmv (and needs its partials).
  * accumulate = 1: out = out + ..., rounded once ((T)((double)out + sum)).  Sums in fp64, no atomics, every order
  * a function of (rowptr, lanes, axis, nb == 1) alone.  PCS_EINVAL before any device call for what pcs_csr_spmv
@@ -249,8 +258,8 @@ int pcs_csr_spmm(int dtype, int axis, int accumulate, int64_t nrows, int64_t nco
  * for k * n <= PCS_KR_MAX_NK and k + n <= PCS_KR_MAX_ROWS (the LDS and register budget derived in the source
  * file); the caller composes larger products.  The forward cuts the l columns into slabs of PCS_KR_SLAB;
  * workgroup g of `ngroups` = ceil(nslabs / spg) <= PCS_KR_MAX_GROUPS sums `spg` consecutive slabs in column
- * order into partials[g * n k ..] (ngroups * n * k doubles, partials_len >= that), and a second kernel adds the
- * groups in order.  Sums in fp64, rounded once, no atomics; the bits depend on (k, n, l, spg) alone.
+ * order into partials[g * n k ..] (ngroups * n * k doubles, partials_len >= that; 8-byte aligned, contents on
+ * entry: arbitrary), and a second kernel adds the groups in order.  Sums in fp64, rounded once, no atomics; the bits depend on (k, n, l, spg) alone.
  * PCS_EINVAL before any device call for an unknown dtype, a negative size, a shape past the limits, a plan that
  * does not tile l, a null or misaligned or short workspace, a null array, or out overlapping an input. */
 #define PCS_KR_SLAB 64
@@ -290,13 +299,15 @@ int pcs_prox_l21_pixel(int dtype, const void* x, void* out, int64_t npix, int d,
 int pcs_fenchel_l21_pixel(int dtype, const void* w, void* out, int64_t npix, int d, double sigma, double lam,
                           hipStream_t stream);
 /* L21Norm.prox with arbitrary labels: `gid[n]` = index of the element's group in
- * [0, ngroups) (np.unique order); ws = ngroups doubles. */
+ * [0, ngroups) (np.unique order); ws = ngroups doubles (8-byte aligned, contents on entry: arbitrary -- the
+ * call clears it). */
 int pcs_prox_l21_labels(int dtype, const void* x, void* out, int64_t n, const int32_t* gid, int64_t ngroups,
                         double tau, void* ws, hipStream_t stream);
 /* The same prox with run-to-run identical group sums (ABI 10; replaces pcs_prox_l21_labels in
  * L21Norm.prox, func/penalty.py:525-560): `order[n]` lists the elements group by group (a stable
  * argsort of gid), `off[ngroups + 1]` the group boundaries in it, `maxlen` the largest group; each
- * group's sum of squares is taken in ascending element order (fp64) without atomics. */
+ * group's sum of squares is taken in ascending element order (fp64) without atomics.  ws = ngroups doubles
+ * (8-byte aligned, contents on entry: arbitrary). */
 int pcs_prox_l21_groups(int dtype, const void* x, void* out, int64_t n, const int32_t* gid, int64_t ngroups,
                         const int32_t* order, const int64_t* off, int64_t maxlen, double tau, void* ws,
                         hipStream_t stream);
@@ -336,7 +347,7 @@ int pcs_prox_entropy(int dtype, const void* x, void* out, int64_t n, double tau,
  * representable values (7 passes fp32, 13 fp64), not to a tolerance in value; all sums are fp64 in a fixed
  * order, so two calls agree bitwise.  19 (fp32) / 31 (fp64) plain launches whatever the data, no host
  * read-back, no atomics: capturable in a hipGraph.  t_dev (device double, may be NULL) receives t.
- * ws >= pcs_thresh_ws_bytes(n), 8-byte aligned.  x == out is allowed.  Arguments are checked before any
+ * ws >= pcs_thresh_ws_bytes(n) (which never decreases in n), 8-byte aligned, contents on entry: arbitrary.  x == out is allowed.  Arguments are checked before any
  * device call; n = 0 is a no-op. */
 enum { PCS_THRESH_SOFT = 0, PCS_THRESH_CLIP = 1 };
 #define PCS_THRESH_PIVOTS 31
@@ -364,11 +375,13 @@ int pcs_sub2(int dtype, const void* x, const void* y, const void* w, void* out, 
 int pcs_mul(int dtype, const void* x, const void* d, void* out, int64_t n, hipStream_t stream);
 /* The two sums of one relative improvement ||old - new|| / ||old|| (proxalgs.py:370-383) in one
  * pass, fixed order: out_dev[0] = sum (old - new)^2, out_dev[1] = sum old^2 (the layout
- * pcs_pds_finalize reads).  ws >= pcs_reduce_ws_bytes(). */
+ * pcs_pds_finalize reads).  ws >= pcs_reduce_ws_bytes(), 8-byte aligned, contents on entry: arbitrary. */
 int pcs_rel_sums(int dtype, const void* old, const void* nw, int64_t n, double* out_dev, void* ws,
                  hipStream_t stream);
 /* Deterministic fp64 reductions into out_dev[0]: kind 0 = sum x^2, 1 = sum |x|,
- * 2 = sum (x-y)^2, 3 = sum x*y.  ws >= pcs_reduce_ws_bytes(). */
+ * 2 = sum (x-y)^2, 3 = sum x*y.  ws >= pcs_reduce_ws_bytes(), 8-byte aligned, contents on entry: arbitrary.
+ * pcs_reduce_ws_bytes() serves every entry point that names it: 2 doubles for each of at most 1024 workgroups;
+ * pcs_apgd_step and pcs_mcmc_accumulate reach its last double once n > 256 * 1023. */
 int64_t pcs_reduce_ws_bytes(void);
 int pcs_reduce(int dtype, int kind, const void* x, const void* y, int64_t n, double* out_dev, void* ws,
                hipStream_t stream);
@@ -379,7 +392,7 @@ int pcs_reduce(int dtype, int kind, const void* x, const void* y, int64_t n, dou
  *                                  PCS_APGD_G_L1 (lam * L1Norm: soft threshold tau*lam)
  *   x'  = x_t + a (x_t - aux)      aux = the previous x_t ('past_aux'), a = (t_old - 1) / t
  * writes x' -> xn, x_t -> aux_n (no aliasing) and sums_dev[0..1] = ||x - x'||^2, ||x||^2 (fp64,
- * fixed order).  ws >= pcs_reduce_ws_bytes(). */
+ * fixed order).  ws >= pcs_reduce_ws_bytes(), 8-byte aligned, contents on entry: arbitrary. */
 enum { PCS_APGD_G_L1 = 3 };
 int pcs_apgd_step(int dtype, const void* x, const void* g, const void* aux, void* xn, void* aux_n, int64_t n,
                   double tau, double a, int gkind, double lam, double seg_a, double seg_b, double* sums_dev,
@@ -407,7 +420,8 @@ int pcs_p2_update_host(int dtype, const void* x, void* heights, int32_t* pos, in
  *   sums_dev[0] = sum x^2, sums_dev[1] = sum S_old^2   (fp64, fixed order, no atomics: the reference's
  *                 diagnostic ||old_sum - new_sum|| / ||old_sum||, the difference being x)
  *   sum += x ; sumsq += x * x ; the K P2 states take x (K = 0: no quantiles, heights / pos / desired unused).
- * ws >= pcs_reduce_ws_bytes().  x, sum and sumsq are distinct arrays. */
+ * ws >= pcs_reduce_ws_bytes(), 8-byte aligned, contents on entry: arbitrary.  x, sum and sumsq are distinct
+ * arrays. */
 int pcs_mcmc_accumulate(int dtype, const void* x, void* sum, void* sumsq, void* heights, int32_t* pos, int64_t n,
                         int K, int64_t count, const double* desired, double* sums_dev, void* ws, hipStream_t stream);
 
@@ -460,11 +474,17 @@ typedef struct {
   const void* taps1;  /* 2H+1 taps along axis 1 (cols), device */
   double tau, sigma, rho, lam, step0, step1, seg_a, seg_b;
   const void* x; void* xn; const void* z; void* zn; const void* y; const void* gbuf;
-  double* partials;       /* [nblocks][4] */
-  void* ctrl;             /* device control block (pcs_ctrl_*) ; NULL = always run */
+  double* partials;       /* [nblocks][4] (pcs_pds2d_nblocks; for pcs_pds2d_run pcs_pds2d_run_nblocks); 16-byte
+                             aligned with hist or sums_out; contents on entry: arbitrary */
+  void* ctrl;             /* device control block (pcs_ctrl_*): pcs_ctrl_bytes() bytes, contents arbitrary
+                             before pcs_ctrl_init / pcs_ctrl_init2 ; NULL = always run */
   double* hist;           /* non-NULL: reduce the partials and run pcs_pds_finalize inside the
-                             step launch (single GPU); NULL: only write `partials` */
-  void* ws;               /* with hist or sums_out: pcs_pds2d_ws_bytes() bytes, zeroed once before first use */
+                             step launch (single GPU); NULL: only write `partials`.  Ctrl.hist_len doubles
+                             (8-byte aligned); contents on entry: arbitrary -- rows [0, Ctrl.it) are written,
+                             the rest is never read or written */
+  void* ws;               /* with hist or sums_out: pcs_pds2d_ws_bytes() bytes, 16-byte aligned, zeroed once
+                             before first use: every counter is reset by its last arriver, so a loop that
+                             stopped, naturally or not, leaves it ready for the next one */
   double* sums_out;       /* hist NULL, sums_out non-NULL (slab mode): the last workgroups reduce the
                              partials, then add pre_partials, into sums_out[4] (no loop control) */
   const double* pre_partials; /* [n_pre][4] partials of an earlier launch of the same iteration */
@@ -518,7 +538,8 @@ typedef struct {
    * pcs_pds2d_run does), in a workgroup of its own while its tasks run: the reduction leaves the
    * critical path of every launch.  The stopping rule then acts one launch later (the extra iterate
    * goes to the buffer the engine does not select: the iterate after Ctrl.it iterations), and the
-   * last launch's partials are finalized by pcs_pds_finalize_pending at the end of a run. */
+   * last launch's partials are finalized by pcs_pds_finalize_pending at the end of a run.  Sized and
+   * aligned as `partials`; contents on entry: arbitrary (Ctrl.pend says whether they are meaningful). */
   const double* fin_partials;
 } pcs_pds2d_args;
 enum { PCS_M_NONE = 0, PCS_M_L1LOSS = 1 };
@@ -609,10 +630,12 @@ typedef struct {
   double tau, lam, seg_a, seg_b;
   const void* x; void* xn; const void* aux; void* aux_n;
   const void* cty;    /* Conv^T y, formed once by the caller */
-  double* partials;   /* [pcs_apgd2d_nblocks()][4] */
+  double* partials;   /* [pcs_apgd2d_nblocks()][4], 16-byte aligned; contents on entry: arbitrary */
   void* ctrl;         /* device control block (pcs_ctrl_init2, has_dual 0) */
-  double* hist;       /* 2 doubles per iteration: the relative improvement, inf */
-  void* ws;           /* pcs_apgd2d_ws_bytes() bytes, zeroed once before first use */
+  double* hist;       /* 2 doubles per iteration: the relative improvement, inf; Ctrl.hist_len doubles,
+                         contents on entry: arbitrary */
+  void* ws;           /* pcs_apgd2d_ws_bytes() bytes, 16-byte aligned, zeroed once before first use (counters
+                         reset by their last arriver, as pcs_pds2d_args.ws) */
 } pcs_apgd2d_args;
 int pcs_apgd2d_supported(const pcs_apgd2d_args* a);
 int64_t pcs_apgd2d_nblocks(const pcs_apgd2d_args* a);
@@ -641,10 +664,10 @@ typedef struct {
   int64_t n0, n1;
   double tau, sigma, rho, lam, step0, step1, w0, w1, seg_a, seg_b;
   const void* x; void* xn; const void* z; void* zn; const void* g;
-  double* partials;
-  void* ctrl;
-  double* hist;
-  void* ws; /* pcs_pds2d_stencil_ws_bytes() bytes, zeroed once before first use */
+  double* partials; /* [pcs_pds2d_stencil_nblocks()][4], 16-byte aligned with hist; contents on entry: arbitrary */
+  void* ctrl;       /* as pcs_pds2d_args.ctrl */
+  double* hist;     /* as pcs_pds2d_args.hist */
+  void* ws; /* pcs_pds2d_stencil_ws_bytes() bytes, 16-byte aligned, zeroed once before first use (as pcs_pds2d_args.ws) */
 } pcs_pds2d_stencil_args;
 int64_t pcs_pds2d_stencil_nblocks(const pcs_pds2d_stencil_args* a);
 int64_t pcs_pds2d_stencil_ws_bytes(const pcs_pds2d_stencil_args* a);
@@ -759,10 +782,12 @@ typedef struct {
   int pad;
   double tau, sigma, rho, lam, step0, step1, step2, seg_a, seg_b;
   const void* x; void* xn; const void* z; void* zn; const void* g;
-  double* partials;       /* [nblocks][4] */
+  double* partials;       /* [nblocks][4] (pcs_pds3d_nblocks / pcs_pds3d_nblocks_bands), 16-byte aligned with hist;
+                             contents on entry: arbitrary */
   void* ctrl;             /* device control block; NULL = always run */
-  double* hist;           /* non-NULL: in-launch reduce + loop control (single GPU) */
-  void* ws;               /* with hist: pcs_pds3d_ws_bytes() bytes, zeroed once */
+  double* hist;           /* non-NULL: in-launch reduce + loop control (single GPU); as pcs_pds2d_args.hist */
+  void* ws;               /* with hist: pcs_pds3d_ws_bytes() bytes, 16-byte aligned, zeroed once before first use
+                             (as pcs_pds2d_args.ws) */
   int kkind;              /* PCS_FORWARD (0), PCS_BACKWARD or PCS_CENTERED: Gradient(kind) */
   int edge;               /* Gradient(edge=...): the centred kind's one-sided end samples */
   /* fkind PCS_F_CONV0 (ABI 5; fp32, forward K): the axis-0 Convolve1D of a separable 3-D PSF inside
@@ -790,8 +815,10 @@ int pcs_pds3d_step_bands(const pcs_pds3d_args* a, int64_t a0, int64_t b0, int64_
 /* Device control block for the hipGraph-captured loop:
  * int32 [0]=it (next iteration), [1]=stopped, [2]=min_iter, [3]=max_iter, [4]=has_dual,
  * [5]=hist_len, [6]=pend (deferred finalization: the last launch's partials wait); double at byte 32:
- * accuracy_threshold.
- * hist: double[2*(max(min_iter,max_iter)+1)+2] = (primal, dual) relative improvement per iteration. */
+ * accuracy_threshold.  pcs_ctrl_bytes() bytes, 8-byte aligned; contents on entry to pcs_ctrl_init /
+ * pcs_ctrl_init2: arbitrary (every field is written).
+ * hist: double[2*(max(min_iter,max_iter)+1)+2] = (primal, dual) relative improvement per iteration; the loop
+ * stops before a row would pass hist_len, the two doubles after the last row are never written. */
 int64_t pcs_ctrl_bytes(void);
 int pcs_ctrl_init(void* ctrl_dev, int min_iter, int max_iter, double thr, int has_dual, hipStream_t stream);
 /* Reduce [nparts][4] partials (fixed order, fp64) into sums[4]. */

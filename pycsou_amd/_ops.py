@@ -116,14 +116,19 @@ def sub2(x, y, w, a, b):
     return out
 
 
-def _ws(t):
-    key = (t.device, 'reduce')
+def _cached_ws(device, kind, nbytes):
+    """A float64 workspace of exactly `nbytes` bytes (the size the C ABI advertises: what a C caller allocates
+    is what these wrappers run on), one per (device, kind, size) and never replaced, so that a captured loop
+    replays with the buffer it was captured with."""
+    key = (device, kind, int(nbytes))
     ws = _ws_cache.get(key)
     if ws is None:
-        lib = L.gpu()
-        ws = torch.empty(int(lib.pcs_reduce_ws_bytes()) // 8 + 8, dtype=torch.float64, device=t.device)
-        _ws_cache[key] = ws
+        ws = _ws_cache[key] = torch.empty(-(-int(nbytes) // 8), dtype=torch.float64, device=device)
     return ws
+
+
+def _ws(t):
+    return _cached_ws(t.device, 'reduce', L.gpu().pcs_reduce_ws_bytes())
 
 
 def reduce_dev(kind, x, y=None, out=None):
@@ -347,15 +352,9 @@ def proj_segment(x, a, b):
 
 
 def _thresh_ws(t):
-    """Workspace of pcs_thresh_l1 (its size does not grow past the kernel's block cap), cached per device
-    like ``_ws`` so that a captured loop replays with the buffer it was captured with."""
-    key = (t.device, 'thresh')
-    ws = _ws_cache.get(key)
-    if ws is None:
-        lib = L.gpu()
-        ws = torch.empty(int(lib.pcs_thresh_ws_bytes(1 << 40)) // 8 + 8, dtype=torch.float64, device=t.device)
-        _ws_cache[key] = ws
-    return ws
+    """Workspace of pcs_thresh_l1 for the elements of `t`: pcs_thresh_ws_bytes(n) bytes (it does not grow past
+    the kernel's block cap, so there are at most that many sizes), cached like ``_ws``."""
+    return _cached_ws(t.device, 'thresh', L.gpu().pcs_thresh_ws_bytes(t.numel()))
 
 
 def thresh_l1(x, a, b, mode, t_out=None):
@@ -456,15 +455,10 @@ def dirderiv(x, v, v_is_field, dims, steps, kind, edge, adjoint=False, scale=1.0
 CUMSUM_SPAN, CUMSUM_SPAN_STRIDED = L.PCS_CUMSUM_SPAN, L.PCS_CUMSUM_SPAN_STRIDED
 
 
-def _cumsum_ws(t):
-    """Workspace of pcs_cumsum (bounded for any shape by PCS_CUMSUM_WS_MAX), cached per device like
-    ``_thresh_ws`` so that a captured loop replays with the buffer it was captured with."""
-    key = (t.device, 'cumsum')
-    ws = _ws_cache.get(key)
-    if ws is None:
-        ws = torch.empty(L.PCS_CUMSUM_WS_MAX // 8, dtype=torch.float64, device=t.device)
-        _ws_cache[key] = ws
-    return ws
+def _cumsum_ws(t, nbytes):
+    """Workspace of pcs_cumsum: the `nbytes` pcs_cumsum_ws_bytes returns for the call (bounded for any shape by
+    PCS_CUMSUM_WS_MAX), cached like ``_ws``; None when the call needs none."""
+    return _cached_ws(t.device, 'cumsum', nbytes) if nbytes > 0 else None
 
 
 def cumsum(x, dims, axis, step, reverse=False, out=None):
@@ -473,13 +467,12 @@ def cumsum(x, dims, axis, step, reverse=False, out=None):
     lib = L.gpu()
     out = torch.empty_like(x) if out is None else out
     d = L.i64s(dims)
-    ws = _cumsum_ws(x)
     need = int(lib.pcs_cumsum_ws_bytes(len(dims), d, int(axis)))
-    if need < 0 or need > ws.numel() * 8 or int(np.prod(dims)) != x.numel() or out.numel() != x.numel() \
+    if need < 0 or need > L.PCS_CUMSUM_WS_MAX or int(np.prod(dims)) != x.numel() or out.numel() != x.numel() \
             or out.dtype != x.dtype or not _dense_on(x.device, x, out):
         raise ValueError('cumsum: shape, axis and tensors do not agree (x and out: contiguous, same dtype, one GPU)')
     L.check(lib.pcs_cumsum(L.dtcode(x), L.ptr(x), L.ptr(out), len(dims), d, int(axis), float(step),
-                           int(bool(reverse)), L.ptr(ws), L.stream()), 'pcs_cumsum')
+                           int(bool(reverse)), L.ptr(_cumsum_ws(x, need)), L.stream()), 'pcs_cumsum')
     return out
 
 

@@ -14,6 +14,16 @@ from .. import _lib as L
 HIST_CHUNK = 4096  # iterations of device history allocated at first; doubled as the loop goes on
 
 
+def loop_buffer(numel, device, fill=None):
+    """Every float64 device buffer a loop owns and lends to the kernels -- the control block, the history,
+    the per-workgroup partials and the reduction workspace -- is allocated here, at exactly the size the
+    C ABI advertises for it (include/pycsou_hip.h: pcs_ctrl_bytes, Ctrl.hist_len, *_nblocks, *_ws_bytes).
+    `fill`: None leaves the contents as they come, else the value of every element."""
+    if fill is None:
+        return torch.empty(int(numel), dtype=torch.float64, device=device)
+    return torch.full((int(numel),), float(fill), dtype=torch.float64, device=device)
+
+
 def initial_rows(total, chunk, up_front=None):
     """History rows allocated when a loop of at most `total` iterations starts: room for the first
     chunks (a max_iter of 1e9 with accuracy_threshold doing the stopping must not allocate
@@ -41,9 +51,9 @@ class LoopControl:
 
     def __init__(self, device):
         self.lib = L.gpu()
-        self.ctrl = torch.zeros(int(self.lib.pcs_ctrl_bytes()) // 8, dtype=torch.float64, device=device)
+        self.ctrl = loop_buffer(int(self.lib.pcs_ctrl_bytes()) // 8, device, 0.0)
         # a placeholder until start(): plans that hold the history pointer can be built before a loop
-        self.hist = torch.full((2,), float('nan'), dtype=torch.float64, device=device)
+        self.hist = loop_buffer(2, device, float('nan'))
         self.total = 0
         self.replaced = False
         self.final = None
@@ -62,7 +72,7 @@ class LoopControl:
         numel = 2 * initial_rows(self.total, chunk, up_front) + 2
         self.replaced = self.hist.numel() < numel
         if self.replaced:
-            self.hist = torch.empty(numel, dtype=torch.float64, device=self.ctrl.device)
+            self.hist = loop_buffer(numel, self.ctrl.device)
         self.hist.fill_(float('nan'))
         L.check(self.lib.pcs_ctrl_init2(L.ptr(self.ctrl), min_iter, max_iter, float(thr), int(has_dual),
                                         int(self.hist.numel()), L.stream()), 'pcs_ctrl_init2')
@@ -82,7 +92,7 @@ class LoopControl:
         cap = grown_rows(have, rows, self.total)
         if cap == have:
             return False
-        new = torch.full((2 * cap + 2,), float('nan'), dtype=torch.float64, device=self.hist.device)
+        new = loop_buffer(2 * cap + 2, self.hist.device, float('nan'))
         new[:self.hist.numel()].copy_(self.hist)
         self._fields()[self.HIST_LEN].fill_(int(new.numel()))
         self.hist = new
@@ -152,12 +162,12 @@ class LoopState(LoopViews):
         self._alloc_partials(a, dev)
         self.ctl = LoopControl(dev)
         a.ctrl = self.ctrl.data_ptr()
-        self.ws = torch.zeros(int(ws_bytes_fn(ctypes.byref(a))) // 8 + 2, dtype=torch.float64, device=dev)
+        self.ws = loop_buffer(-(-int(ws_bytes_fn(ctypes.byref(a))) // 8), dev, 0.0)
         a.ws = self.ws.data_ptr()
 
     def _alloc_partials(self, a, dev):
         """[nblocks][4] doubles."""
-        self.partials = torch.empty(4 * self.nblocks, dtype=torch.float64, device=dev)
+        self.partials = loop_buffer(4 * self.nblocks, dev)
         a.partials = self.partials.data_ptr()
 
 

@@ -33,6 +33,7 @@ from ..func.penalty import L1Norm, L21Norm, SquaredL2Norm
 from ..linop.base import HomothetyMap
 from ..linop.conv import Convolve2DOp
 from ..linop.diff import GradientOp, LaplacianOp
+from . import _loop
 from ._loop import LaunchTimer, LoopState
 
 # images at least this large launch chunks from C instead of replaying a captured graph
@@ -483,7 +484,7 @@ class PDS2DEngine(LoopState):
             self.run_nblocks = int(query(self.lib.pcs_pds2d_run_nblocks, a, -1, partials=a.x))
             cap = max(cap, self.run_nblocks, int(query(self.lib.pcs_pds2d_run_nblocks, a, 1, partials=a.x)))
         nb4 = cap * 4
-        self.partials = torch.empty((2 if defer else 1) * nb4, dtype=torch.float64, device=dev)
+        self.partials = _loop.loop_buffer((2 if defer else 1) * nb4, dev)
         self.part_halves = [self.partials[:nb4], self.partials[nb4:]] if defer else [self.partials]
         a.partials = self.partials.data_ptr()
         if defer:

@@ -36,6 +36,7 @@ from ..core.linop import LinOpComp
 from ..linop.conv import Convolve1DOp
 from ..linop.diff import GradientOp
 from ..parallel.slab import SlabLayout
+from . import _loop
 from ._loop import LaunchTimer, LoopState, capture_agreed, worst_over_ranks
 from .engine import fused_spec, match_f, match_g, match_h, query
 
@@ -392,7 +393,7 @@ class PDS3DEngine(LoopState):
             raise ValueError('banded 3-D step unavailable for this slab')
         need = 4 * sum(self.nb_bands)
         if self.partials.numel() < need:
-            self.partials = torch.empty(need, dtype=torch.float64, device=self.partials.device)
+            self.partials = _loop.loop_buffer(need, self.partials.device)
             for q in (0, 1):
                 self.args[q].partials = self.partials.data_ptr()
 

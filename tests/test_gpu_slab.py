@@ -427,6 +427,40 @@ def test_slab3d_general_k_bitwise(name, world):
         assert torch.equal(z2, z1), (dtype, (z2 - z1).abs().max().item())
 
 
+@pytest.mark.parametrize('name,world', [('denoise3d_l21_cen_16', 2), ('denoise3d_l21_cen_16', 3),
+                                        ('deconv3d_l1_bwd_20_sep7', 2)])
+def test_slab3d_general_k_stale_halo_plane(name, world):
+    """Backward / centred 3-D K stores two z halo planes per side but exchanges the outer one for z0 only
+    (zdepth = (2, 1, 1)): the outer z1 / z2 plane keeps whatever it held at construction.  Here it holds NaN,
+    on both sides of every rank and in both buffer parities: x and z stay bitwise the single-GPU iterate and
+    the history has no NaN, so no kernel reads that plane."""
+    from pycsou_amd.opt.engine3d import PDS3DEngine
+    from pycsou_amd.parallel import run_local
+    for dtype in (np.float64, np.float32):
+        c = pds_case(name)
+        pds = build(c, dtype, engine='fused')
+        spec, dt = pds._fused_spec(), pds._compute_dtype()
+        run = (pds.max_iter, pds.min_iter, pds.accuracy_threshold)
+        n1, x1, z1, h1 = PDS3DEngine(spec, dt, pds.tau, pds.sigma, pds.rho, pds.x0, pds.z0).run(*run)
+        slabs = [PDS3DEngine(spec, dt, pds.tau, pds.sigma, pds.rho, pds.x0, pds.z0, rank=r, world=world)
+                 for r in range(world)]
+        for s in slabs:
+            assert s.hz == 2 and s.zdepth == (2, 1, 1)
+            for q in (0, 1):
+                for comp in (1, 2):
+                    for lo in (-2, s.rows + 1):     # the outer of the two stored planes, below and above
+                        s.lay.rows_view(s.Z[q], s.hz, lo, lo + 1, comp).fill_(float('nan'))
+            assert int(torch.isnan(s.Z[0]).sum()) == 4 * s.lay.n1
+        res = run_local(slabs, *run)
+        assert all(r[0] == n1 == int(c['n_iter']) for r in res)
+        x2 = torch.cat([r[1] for r in res])
+        z2 = torch.cat([torch.cat([r[2].view(3, -1)[k] for r in res]) for k in range(3)])
+        assert torch.equal(x2, x1), (dtype, (x2 - x1).abs().max().item())
+        assert torch.equal(z2, z1), (dtype, (z2 - z1).abs().max().item())
+        for r in res:
+            assert not np.isnan(np.asarray(r[3])[:n1]).any(), 'NaN in the history'
+
+
 @pytest.mark.parametrize('kind', ['centered', 'backward'])
 def test_slab3d_banded_general_k_bitwise(kind):
     """The banded 3-D order with a backward / centred K (g of the plane before each band too):
