@@ -8,6 +8,8 @@ OBJ := $(patsubst pycsou_amd/csrc/%.hip,build/%.o,$(SRC))
 FLAGS := --offload-arch=$(ARCH) -O3 -fno-slp-vectorize -fPIC -std=c++17 -Wall -Wno-unused-function -Iinclude
 # mcmc.hip: running sums and P2 markers must round as NumPy does (no a*b+c -> fma)
 FLAGS_mcmc := -ffp-contract=off
+# cg.hip: the CG recurrences round as SciPy's do (p *= beta; p += r is two roundings)
+FLAGS_cg := -ffp-contract=off
 
 all: $(LIB)
 

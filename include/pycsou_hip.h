@@ -838,6 +838,59 @@ int pcs_pds_finalize_pending(const double* partials, int64_t nparts, void* ctrl_
 int pcs_ctrl_init2(void* ctrl_dev, int min_iter, int max_iter, double thr, int has_dual, int hist_len,
                    hipStream_t stream);
 
+/* ---------------------------------------------------------------- pseudo-inverse: batched conjugate gradients */
+
+/* The solver between two operator applications of LinearOperator.pinv / LinOpPinv (pycsou/core/linop.py:397-420,
+ * 618-629 -> pylops NormalEquationsInversion(Op, None, y, epsI=eps) -> scipy.sparse.linalg.cg on
+ * (A^T A + eps^2 I) x = A^T y; SciPy 1.15: x0 = 0 unless given, stop when ||r|| < max(atol, rtol ||b||),
+ * rtol = 1e-5, maxiter = 10 n).  PyLops only forwards; the contract restated here is SciPy's cg.
+ *
+ * nb >= 1 independent systems; system j is row j of contiguous (nb, n) arrays x, r, p, q, b.  One iteration:
+ *   pcs_cg_dir     p_j = beta_j p_j + r_j              (p_j = r_j while the control block's it == 0)
+ *   caller         q = A^T (A p)                       (rows of p -> rows of q)
+ *   pcs_cg_dot     pq_j = sum p (q + eps2 p),  alpha_j = rho_j / pq_j
+ *   pcs_cg_update  x_j += alpha_j p_j,  r_j -= alpha_j (q_j + eps2 p_j),  rho' = sum r_j r_j,
+ *                  beta_j = rho' / rho_j,  rho_j = rho',  active_j &= !(sqrt(rho') < tol_j),  it += 1,
+ *                  stopped when no system is active or it == max_iter (or the history is full),
+ *                  hist[2 it], hist[2 it + 1] = max_j ||r_j|| / ||b_j|| (0 where b_j = 0), active systems
+ * SciPy's recurrences operation for operation (no contraction into fma), so an fp64 run differs from SciPy by
+ * the summation order alone.  Vectors in `dtype`; sums and scalars in fp64, scalars rounded to `dtype` where
+ * they multiply a vector; eps2 = eps^2 is applied on the fly, q is never rewritten.  Traffic per system and
+ * iteration: dir 2n + n, dot 2n, update 4n + 2n words.
+ * An inactive system is not written at all (x, r, p keep their bits); once the control block's `stopped` is
+ * set every launch returns without writing, so replays of a captured chunk past the stop change nothing.
+ * Breakdown: pq_j not > 0 or not finite sets breakdown_j = 1 and active_j = 0 (SciPy goes on and returns
+ * inf / NaN there).
+ * Sums: per-workgroup partials, then a finalising launch adds a system's partials in a fixed order; no
+ * atomics, the bits depend on n and on the access path alone (16-byte loads and stores when n sizeof(dtype) is
+ * a multiple of 16 and every base is 16-byte aligned, element-wise otherwise), not on nb or the run.
+ * Grid: blockIdx.y = system, min(ceil(n / 256), PCS_CG_MAX_BLOCKS) workgroups per system, grid-stride over n.
+ *
+ * state:    pcs_cg_state_bytes(nb) bytes, 8-byte aligned: per system 8 doubles rho, pq, alpha, beta, tol, ||b||,
+ *           active, breakdown.  Contents on entry to pcs_cg_init: arbitrary (it writes every field); the other
+ *           entries read what pcs_cg_init and they have written.
+ * partials: pcs_cg_nblocks(n, nb) doubles ([nb][workgroups per system]), 8-byte aligned; contents on entry:
+ *           arbitrary (a finalising launch reads only what the launch before it has written).
+ * ctrl:     the control block above (pcs_ctrl_bytes()); pcs_cg_init writes every field (it = 0, min_iter = 0,
+ *           max_iter, hist_len, stopped when no system is active or max_iter == 0).
+ * hist:     hist_len doubles, rows of 2; never written past hist_len (pcs_cg_init does not write it).
+ * pcs_cg_init: on entry r holds the initial residual (b, or b - (A^T A + eps^2 I) x0); writes ||b_j||,
+ *           tol_j = max(atol, rtol ||b_j||), rho_j = r_j . r_j, active_j = ||b_j|| > 0 and not ||r_j|| < tol_j.
+ * PCS_EINVAL before any device call: null pointer, n < 0, nb < 1, unknown dtype, max_iter < 0, hist_len < 2,
+ * negative or non-finite rtol / atol / eps2, overlap among x, r, p, q.  PCS_EUNSUPPORTED: nb > 65535 (split the
+ * batch).  pcs_cg_state_bytes / pcs_cg_nblocks return PCS_EINVAL for n < 0 or nb < 1. */
+#define PCS_CG_MAX_BLOCKS 1024
+int64_t pcs_cg_state_bytes(int64_t nb);
+int64_t pcs_cg_nblocks(int64_t n, int64_t nb);
+int pcs_cg_init(int dtype, const void* b, const void* r, int64_t n, int64_t nb, double rtol, double atol, int max_iter,
+                void* state, double* partials, void* ctrl, double* hist, int hist_len, hipStream_t stream);
+int pcs_cg_dir(int dtype, const void* r, void* p, int64_t n, int64_t nb, const void* state, const void* ctrl,
+               hipStream_t stream);
+int pcs_cg_dot(int dtype, const void* p, const void* q, int64_t n, int64_t nb, double eps2, void* state,
+               double* partials, const void* ctrl, hipStream_t stream);
+int pcs_cg_update(int dtype, void* x, void* r, const void* p, const void* q, int64_t n, int64_t nb, double eps2,
+                  void* state, double* partials, void* ctrl, double* hist, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,8 @@ PCS_CUMSUM_WS_MAX = 2 * 1024 * 1024 + 64 * 1024
 PCS_SPMV_LONG_ROW, PCS_SPMV_CHUNK = 4096, 4096
 # pcs_khatri_rao_*: column slab, the fused limits k n <= MAX_NK and k + n <= MAX_ROWS, most workgroups of the forward
 PCS_KR_SLAB, PCS_KR_MAX_NK, PCS_KR_MAX_ROWS, PCS_KR_MAX_GROUPS = 64, 1024, 120, 512
+# pcs_cg_*: most workgroups per system, systems per launch (grid y)
+PCS_CG_MAX_BLOCKS, PCS_CG_MAX_NB = 1024, 65535
 PCS_F_NULL, PCS_F_DENOISE, PCS_F_SEPCONV, PCS_F_GRADBUF, PCS_F_CONV2D, PCS_F_CONV0 = 0, 1, 2, 3, 4, 5
 PCS_M_NONE, PCS_M_L1LOSS = 0, 1
 # pcs_pds2d_path: the kernel family of a fused 2-D step
@@ -243,6 +245,13 @@ _SIGS = {
     'pcs_pds_finalize': (_c_int, [_vp, _vp, _vp, _vp]),
     'pcs_pds_reduce_finalize': (_c_int, [_vp, _c_i64, _vp, _vp, _vp]),
     'pcs_pds_finalize_pending': (_c_int, [_vp, _c_i64, _vp, _vp, _vp]),
+    'pcs_cg_state_bytes': (_c_i64, [_c_i64]),
+    'pcs_cg_nblocks': (_c_i64, [_c_i64, _c_i64]),
+    'pcs_cg_init': (_c_int, [_c_int, _vp, _vp, _c_i64, _c_i64, _c_dbl, _c_dbl, _c_int, _vp, _vp, _vp, _vp, _c_int,
+                             _vp]),
+    'pcs_cg_dir': (_c_int, [_c_int, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp]),
+    'pcs_cg_dot': (_c_int, [_c_int, _vp, _vp, _c_i64, _c_i64, _c_dbl, _vp, _vp, _vp, _vp]),
+    'pcs_cg_update': (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_dbl, _vp, _vp, _vp, _vp, _vp]),
 }
 
 EXPORTS = tuple(_SIGS)

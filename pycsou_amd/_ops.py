@@ -800,3 +800,183 @@ def conv1d(x, dims, axis, taps_dev, k, off):
 
 def scalar(x):
     return isinstance(x, Number)
+
+
+# ---------------------------------------------------------------- pseudo-inverse: batched CG on the normal equations
+
+# pcs_cg_*: most workgroups per system (the grid-stride loop takes a second pass from CG_MAX_BLOCKS * 256 + 1
+# elements), most systems per launch, iterations per captured chunk
+CG_MAX_BLOCKS, CG_MAX_NB, CG_CHUNK = L.PCS_CG_MAX_BLOCKS, L.PCS_CG_MAX_NB, 8
+CG_RHO, CG_PQ, CG_ALPHA, CG_BETA, CG_TOL, CG_BNRM, CG_ACTIVE, CG_BREAKDOWN = range(8)   # doubles of one system's state
+
+
+def cg_state(nb, dev):
+    """The state block of `nb` systems, (nb, 8) float64 at exactly pcs_cg_state_bytes(nb) bytes."""
+    return torch.empty(int(L.gpu().pcs_cg_state_bytes(int(nb))) // 8, dtype=torch.float64, device=dev).view(int(nb), 8)
+
+
+def cg_partials(n, nb, dev):
+    """The per-workgroup partial sums of `nb` systems of `n` unknowns: pcs_cg_nblocks(n, nb) doubles."""
+    return torch.empty(int(L.gpu().pcs_cg_nblocks(int(n), int(nb))), dtype=torch.float64, device=dev)
+
+
+def _cg_rows(name, first, *more):
+    """(n, nb) of contiguous (nb, n) tensors of one dtype on one GPU."""
+    if first.dim() != 2 or any(t.shape != first.shape or t.dtype != first.dtype for t in more) \
+            or not _dense_on(first.device, first, *more):
+        raise ValueError(f'{name}: the vectors must be contiguous (nb, n) tensors of one shape and dtype on one GPU')
+    return int(first.shape[1]), int(first.shape[0])
+
+
+def cg_init(B, R, rtol, atol, max_iter, state, partials, ctrl, hist):
+    """``pcs_cg_init``: with ``R`` the initial residual, ||b_j||, tol_j, rho_j and active_j of every system and
+    the loop control."""
+    n, nb = _cg_rows('cg_init', B, R)
+    L.check(L.gpu().pcs_cg_init(L.dtcode(B), L.ptr(B), L.ptr(R), n, nb, float(rtol), float(atol), int(max_iter),
+                                L.ptr(state), L.ptr(partials), L.ptr(ctrl), L.ptr(hist), int(hist.numel()),
+                                L.stream()), 'pcs_cg_init')
+
+
+def cg_dir(R, P, state, ctrl):
+    """``pcs_cg_dir``: P_j = beta_j P_j + R_j (P_j = R_j on iteration 0)."""
+    n, nb = _cg_rows('cg_dir', R, P)
+    L.check(L.gpu().pcs_cg_dir(L.dtcode(R), L.ptr(R), L.ptr(P), n, nb, L.ptr(state), L.ptr(ctrl), L.stream()),
+            'pcs_cg_dir')
+
+
+def cg_dot(P, Q, eps2, state, partials, ctrl):
+    """``pcs_cg_dot``: pq_j = sum P_j (Q_j + eps2 P_j) and alpha_j = rho_j / pq_j."""
+    n, nb = _cg_rows('cg_dot', P, Q)
+    L.check(L.gpu().pcs_cg_dot(L.dtcode(P), L.ptr(P), L.ptr(Q), n, nb, float(eps2), L.ptr(state), L.ptr(partials),
+                               L.ptr(ctrl), L.stream()), 'pcs_cg_dot')
+
+
+def cg_update(X, R, P, Q, eps2, state, partials, ctrl, hist):
+    """``pcs_cg_update``: X_j += alpha_j P_j, R_j -= alpha_j (Q_j + eps2 P_j), then rho, beta, the stop test, the
+    iteration count and one history row."""
+    n, nb = _cg_rows('cg_update', X, R, P, Q)
+    L.check(L.gpu().pcs_cg_update(L.dtcode(X), L.ptr(X), L.ptr(R), L.ptr(P), L.ptr(Q), n, nb, float(eps2),
+                                  L.ptr(state), L.ptr(partials), L.ptr(ctrl), L.ptr(hist), L.stream()),
+            'pcs_cg_update')
+
+
+class CGInfo:
+    """What a solve leaves beside X: per-system ``rnorm`` (||r_j||), ``active`` and ``breakdown`` (NumPy arrays)
+    and ``hist``, one row per iteration: (max_j ||r_j|| / ||b_j||, active systems after it)."""
+
+    def __init__(self, rnorm, active, breakdown, hist):
+        self.rnorm, self.active, self.breakdown, self.hist = rnorm, active, breakdown, hist
+
+
+class CGNormal:
+    """The buffers and the captured chunk of CG on ``(A^T A + eps^2 I) x = A^T y`` for one operator, batch size,
+    dtype and eps (1 <= nb <= CG_MAX_NB).  One iteration is ``pcs_cg_dir``, ``Q = A^T (A P)`` through
+    ``_apply_cols``, ``pcs_cg_dot``, ``pcs_cg_update``; ``chunk`` iterations are captured into one hipGraph
+    (eager launches when the capture fails or ``use_graph`` is off) and the stop decision is read back
+    asynchronously, one chunk behind -- the iterations issued past the stop write nothing."""
+
+    def __init__(self, op, nb, dtype, eps, chunk=CG_CHUNK, use_graph=True):
+        from .opt._loop import LoopControl
+        dev = device()
+        self.op, self.nb, self.n, self.dtype = op, int(nb), int(op.shape[1]), dtype
+        self.eps2, self.chunk, self.use_graph = float(eps) ** 2, max(1, int(chunk)), bool(use_graph)
+        self.X, self.R, self.P = (torch.zeros((self.nb, self.n), dtype=dtype, device=dev) for _ in range(3))
+        self.state, self.partials = cg_state(self.nb, dev), cg_partials(self.n, self.nb, dev)
+        self.ctl = LoopControl(dev)
+        self.graph = None
+
+    def adjoint(self, Y):
+        """A^T on the rows of Y; a single row goes through ``_adj`` (no line loop, no stacking copy)."""
+        if self.nb == 1:
+            return self.op._adj(Y.reshape(-1)).reshape(1, -1).contiguous()
+        return self.op._apply_cols(Y, 1, adjoint=True).contiguous()
+
+    def normal(self, P):
+        """A^T (A P) on the rows of P, never P's own storage."""
+        Q = self.adjoint(self.op._apply(P.reshape(-1)).reshape(1, -1) if self.nb == 1 else self.op._apply_cols(P, 1))
+        return Q.clone() if Q.data_ptr() == P.data_ptr() else Q
+
+    def _iteration(self):
+        cg_dir(self.R, self.P, self.state, self.ctl.ctrl)
+        Q = self.normal(self.P)
+        cg_dot(self.P, Q, self.eps2, self.state, self.partials, self.ctl.ctrl)
+        cg_update(self.X, self.R, self.P, Q, self.eps2, self.state, self.partials, self.ctl.ctrl, self.ctl.hist)
+
+    def _chunk(self):
+        for _ in range(self.chunk):
+            self._iteration()
+
+    def solve(self, Y, rtol=1e-5, atol=0.0, maxiter=None, x0=None):
+        """X (a new (nb, n) tensor), the iteration count and a CGInfo for the rows of ``Y`` (nb, m)."""
+        from .opt._loop import capture_agreed
+        if Y.dim() != 2 or Y.shape != (self.nb, self.op.shape[0]) or Y.dtype != self.dtype:
+            raise ValueError(f'CGNormal.solve: Y must be a ({self.nb}, {self.op.shape[0]}) {self.dtype} tensor')
+        maxiter = min(10 * self.n if maxiter is None else int(maxiter), 2 ** 31 - 2)
+        B = self.adjoint(Y.contiguous())
+        if x0 is None:
+            self.X.zero_()
+            self.R.copy_(B)
+        else:
+            self.X.copy_(x0.reshape(self.nb, self.n))
+            self.R.copy_(B - (self.normal(self.X) + self.eps2 * self.X))      # scipy: r = b - matvec(x)
+        ctl = self.ctl
+        ctl.start(maxiter, 0, 0.0, False, chunk=self.chunk)
+        if ctl.replaced:
+            self.graph = None
+        cg_init(B, self.R, rtol, atol, maxiter, self.state, self.partials, ctl.ctrl, ctl.hist)
+        issued = 0
+        if maxiter > 0:
+            self._iteration()       # eager: whatever the operator builds on first use is built outside a capture
+            issued = 1
+            ctl.read_async()
+        while issued < maxiter:
+            if ctl.reserve(issued + self.chunk + 2):
+                self.graph = None   # the captured chunk holds the history pointer
+            if self.use_graph and self.graph is None:
+                if ctl.poll(lag=0, drain=True) is not None:     # a capture synchronises anyway: already done?
+                    break
+                self.graph = capture_agreed(self._chunk)
+                self.use_graph = self.graph is not None
+            if self.graph is not None:
+                self.graph.replay()
+            else:
+                self._chunk()
+            issued += self.chunk
+            ctl.read_async()
+            if ctl.poll(lag=1) is not None:     # one chunk in flight behind the one whose control is read
+                break
+        torch.cuda.synchronize()
+        it = ctl.iterations()
+        st = self.state.cpu().numpy()
+        if x0 is not None and np.any(st[:, CG_BNRM] == 0):                  # scipy: `if bnrm2 == 0: return b`
+            self.X[torch.as_tensor(st[:, CG_BNRM] == 0).to(self.X.device)] = 0
+        info = CGInfo(np.sqrt(st[:, CG_RHO]), st[:, CG_ACTIVE] != 0, st[:, CG_BREAKDOWN] != 0, ctl.rows(it).copy())
+        return self.X.clone(), it, info
+
+
+def cg_normal(op, Y, eps, rtol=1e-5, atol=0.0, maxiter=None, x0=None, chunk=CG_CHUNK, use_graph=True, plans=None):
+    """``(A^T A + eps^2 I) X_j = A^T Y_j`` for the rows of the (nb, m) device tensor ``Y`` by conjugate gradients
+    with SciPy's ``cg`` semantics (x0 = 0 unless given, stop when ||r|| < max(atol, rtol ||b||), maxiter = 10 n):
+    returns X (nb, n), the iteration count (the most over the batch) and a CGInfo.  ``plans``: a dict in which
+    the CGNormal of each (batch size, dtype, chunk, use_graph) is kept for the next call.  A batch of more than
+    CG_MAX_NB systems is solved in slices."""
+    Y = Y.contiguous()
+    nb = int(Y.shape[0])
+    if nb == 0:
+        return torch.empty((0, op.shape[1]), dtype=Y.dtype, device=Y.device), 0, \
+            CGInfo(np.zeros(0), np.zeros(0, bool), np.zeros(0, bool), np.zeros((0, 2)))
+    plans = {} if plans is None else plans
+    parts = []
+    for s in range(0, nb, CG_MAX_NB):
+        Ys = Y[s:s + CG_MAX_NB]
+        key = (int(Ys.shape[0]), Y.dtype, int(chunk), bool(use_graph))
+        plan = plans.get(key)
+        if plan is None:
+            plan = plans[key] = CGNormal(op, Ys.shape[0], Y.dtype, eps, chunk, use_graph)
+        xs = None if x0 is None else x0.reshape(nb, -1)[s:s + CG_MAX_NB]
+        parts.append(plan.solve(Ys, rtol, atol, maxiter, xs))
+    if len(parts) == 1:
+        return parts[0]
+    info = CGInfo(*(np.concatenate([getattr(p[2], f) for p in parts]) for f in ('rnorm', 'active', 'breakdown')),
+                  parts[int(np.argmax([p[1] for p in parts]))][2].hist)
+    return torch.cat([p[0] for p in parts]), max(p[1] for p in parts), info

@@ -10,6 +10,11 @@ algebra (``linop.py:442-553``).  Subclasses implement the device-level ``_apply`
 host loop of tens to hundreds of operator applications) by a device Lanczos iteration
 on ``K^T K`` in O(1) vectors: every operator application and the recurrence stay on the
 GPU, only the small tridiagonal eigenproblem runs on the host every few steps.
+
+``pinv`` / ``PinvOp`` / ``dagger`` / ``LinOpPinv`` (``linop.py:397-440, 618-629``) replace PyLops'
+``NormalEquationsInversion`` (SciPy ``cg`` on the normal equations) by batched conjugate gradients on the device
+(``_ops.cg_normal``, ``csrc/cg.hip``); ``todense`` / ``tosparse`` / ``cond`` (``linop.py:323-395``) go through the
+dense matrix, which stays on the device.
 """
 
 import warnings
@@ -229,6 +234,75 @@ class LinearOperator(DifferentiableMap):
             self.lipschitz_cst = float(np.sqrt(max(lam, 0.0)))
         self.diff_lipschitz_cst = self.lipschitz_cst
 
+    # -- explicit forms, condition number, pseudo-inverse (linop.py:323-440)
+    TODENSE_BLOCK = 1024    # identity columns per _apply_cols call of todense
+    COND_MAX = 2048         # largest min(shape) cond() takes
+
+    def todense(self, dtype=None):
+        """The operator as a ``DenseLinearOperator`` whose matrix stays on the device (``linop.py:323-334``):
+        ``_apply_cols`` on blocks of at most ``TODENSE_BLOCK`` columns of the identity, in the operator's
+        compute dtype unless ``dtype`` (a torch dtype) says otherwise."""
+        from ..linop.base import DenseLinearOperator
+        dt = self._compute_dtype() if dtype is None else dtype
+        m, n = self.shape
+        dev = O.device()
+        M = torch.empty((m, n), dtype=dt, device=dev)
+        for c0 in range(0, n, self.TODENSE_BLOCK):
+            k = min(self.TODENSE_BLOCK, n - c0)
+            E = torch.zeros((n, k), dtype=dt, device=dev)
+            E[c0:c0 + k] = torch.eye(k, dtype=dt, device=dev)
+            M[:, c0:c0 + k] = self._apply_cols(E, 0)
+        return DenseLinearOperator(M, is_symmetric=self.is_symmetric)
+
+    def tosparse(self):
+        """``linop.py:336-347``: the CSR matrix of ``todense()``."""
+        import scipy.sparse as sp
+        from ..linop.base import SparseLinearOperator
+        return SparseLinearOperator(sp.csr_matrix(self.todense().mat.cpu().numpy()), is_symmetric=self.is_symmetric)
+
+    def cond(self, **kwargs):
+        """Condition number (``linop.py:381-395``): largest over smallest nonzero singular value (those above
+        ``max(shape) eps sigma_max``, NumPy's rank convention), from ``torch.linalg.svdvals`` of the fp64
+        ``todense()``.  The dense route serves ``min(shape) <= COND_MAX``; PyLops' keyword arguments are accepted
+        and ignored."""
+        if min(self.shape) > self.COND_MAX:
+            raise NotImplementedError(f'cond() forms the dense matrix and serves min(shape) <= {self.COND_MAX}, '
+                                      f'got shape {self.shape}')
+        s = torch.linalg.svdvals(self.todense(dtype=torch.float64).mat).cpu().numpy()
+        if s.size == 0 or not s[0] > 0:
+            return float('inf')
+        s = s[s > max(self.shape) * np.finfo(np.float64).eps * s[0]]
+        return float(s[0] / s[-1])
+
+    def pinv(self, y, eps=0, **kwargs):
+        """Pseudo-inverse at ``y`` (``linop.py:397-420``): conjugate gradients on the normal equations
+        ``(A^T A + eps^2 I) x = A^T y`` on the device (``_ops.cg_normal``) with the semantics of
+        ``scipy.sparse.linalg.cg``, which PyLops' ``NormalEquationsInversion`` hands its keyword arguments to:
+        ``rtol`` (or ``tol``), ``atol``, ``maxiter`` and ``x0`` are honoured, any other is accepted and ignored."""
+        if isinstance(y, Number):
+            y = np.asarray([y], dtype=float)
+        t = O.to_dev(y)
+        kwargs = dict(kwargs)
+        x0 = kwargs.pop('x0', None)
+        x0 = None if x0 is None else O.to_dev(x0, t.dtype)
+        return O.like(LinOpPinv(self, eps).solve(t.reshape(1, -1), x0=x0, **kwargs)[0].reshape(-1), y)
+
+    @property
+    def PinvOp(self):
+        return LinOpPinv(self)
+
+    @property
+    def dagger(self):
+        return self.PinvOp
+
+    @property
+    def RowProjector(self):
+        return SymmetricLinearOperator(self.dagger * self)
+
+    @property
+    def ColProjector(self):
+        return SymmetricLinearOperator(self * self.dagger)
+
     # -- algebra (linop.py:442-485)
     def __add__(self, other):
         if isinstance(other, LinearOperator):
@@ -415,3 +489,55 @@ class UnitaryOperator(LinearOperator):
 
     def cond(self, **kwargs):
         return 1
+
+
+class LinOpPinv(LinearOperator):
+    """Pseudo-inverse of ``LinOp`` with Tikhonov damping ``eps`` as an operator (``linop.py:618-629``): applying
+    it solves ``(A^T A + eps^2 I) x = A^T y`` by conjugate gradients on the device (``_ops.cg_normal``; SciPy's
+    ``cg`` defaults: x0 = 0, rtol = 1e-5, maxiter = 10 n).  ``_apply_cols`` solves all the lines of a matrix as
+    one batch -- what ``KroneckerProduct.PinvOp`` runs on -- and the adjoint is the pseudo-inverse of ``LinOp.H``.
+    ``last``: iteration count and ``CGInfo`` of the most recent solve.  A system whose ``p . N p`` is not
+    positive (a breakdown, where SciPy would return inf / NaN) stops where it is, with a warning."""
+
+    def __init__(self, LinOp, eps=0):
+        self.LinOp = LinOp
+        self.eps = eps
+        super().__init__(shape=LinOp.H.shape, dtype=LinOp.dtype, is_explicit=False, is_dense=False, is_dask=False,
+                         is_symmetric=LinOp.is_symmetric)
+        self._plans = {}
+        self._adjoint = None
+        self.last = None
+
+    def solve(self, Y, x0=None, **kwargs):
+        """The rows of the (nb, m) device tensor ``Y``: (X, iterations, CGInfo); ``kwargs`` as ``pinv`` takes."""
+        rtol = kwargs.get('rtol', kwargs.get('tol', 1e-5))
+        opts = {k: kwargs[k] for k in ('chunk', 'use_graph') if k in kwargs}
+        X, it, info = O.cg_normal(self.LinOp, Y, self.eps, rtol=rtol, atol=kwargs.get('atol', 0.0),
+                                  maxiter=kwargs.get('maxiter'), x0=x0, plans=self._plans, **opts)
+        if info.breakdown.any():
+            warnings.warn(f'pinv: conjugate gradients broke down (p . N p not positive) in '
+                          f'{int(info.breakdown.sum())} of {len(info.breakdown)} system(s); their iterates are '
+                          f'returned as they stood')
+        self.last = (it, info)
+        return X, it, info
+
+    def _apply(self, t):
+        return self.solve(t.reshape(1, -1))[0].reshape(-1)
+
+    def _adj(self, t):
+        return self.get_adjointOp()._apply(t)
+
+    def get_adjointOp(self):
+        if self.is_symmetric:
+            return self
+        if self._adjoint is None:
+            self._adjoint = LinOpPinv(self.LinOp.H, self.eps)
+            self._adjoint._adjoint = self
+        return self._adjoint
+
+    def _apply_cols(self, T, axis, adjoint=False):
+        if adjoint and not self.is_symmetric:
+            return self.get_adjointOp()._apply_cols(T, axis)
+        if axis == 1:
+            return self.solve(T)[0]
+        return self.solve(T.t().contiguous())[0].t().contiguous()

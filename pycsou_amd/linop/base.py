@@ -333,6 +333,12 @@ class KroneckerProduct(LinearOperator):
                 op.compute_lipschitz_cst(**kwargs)
         self.lipschitz_cst = self.diff_lipschitz_cst = float(self.linop1.lipschitz_cst * self.linop2.lipschitz_cst)
 
+    @property
+    def PinvOp(self):
+        """``(A (x) B)^+ = A^+ (x) B^+`` (``base.py:802-803``): each factor's pseudo-inverse solves all the lines
+        of the reshaped vector as one batch (``LinOpPinv._apply_cols``)."""
+        return KroneckerProduct(self.linop1.PinvOp, self.linop2.PinvOp)
+
 
 def _lip_product(op1, op2):
     a, b = op1.lipschitz_cst, op2.lipschitz_cst
