@@ -272,6 +272,52 @@ int pcs_khatri_rao_fwd(int dtype, const void* A, const void* B, const void* x, v
 int pcs_khatri_rao_adj(int dtype, const void* A, const void* B, const void* Y, void* out, int64_t k, int64_t n,
                        int64_t l, hipStream_t stream);
 
+/* Green functions (pycsou/math/green.py) and the matrix-free MappedDistanceMatrix built on them
+ * (csrc/green_core.hpp, csrc/mdm.hip; pycsou/linop/sampling.py:772-1058).  A function is (kind, k, p0, p1):
+ *   PCS_GREEN_MATERN / PCS_GREEN_WENDLAND   k in 0..3, p0 = epsilon > 0
+ *   PCS_GREEN_SUBGAUSSIAN                   p0 = alpha in (0, 2), p1 = epsilon > 0 (k unused)
+ *   PCS_GREEN_CAUSAL_ITER                   k >= 1:  t^(k-1) [t >= 0]
+ *   PCS_GREEN_CAUSAL_EXP                    k >= 1, p0 = alpha > 0:  t^(k-1) exp(-alpha t) [t >= 0]
+ * Negative arguments as NumPy: the causal mask gives 0, SubGaussian NaN, Matern and Wendland their formulas.
+ *   pcs_green_eval:  out[i] = phi(r[i])  (out == r allowed).
+ *   pcs_mdm_apply:   out[i] = sum_j phi(d(P_i, Q_j)) x[j],  P (nrows x dim), Q (ncols x dim) row-major,
+ *                    dim in 1..PCS_MDM_MAX_DIM; the adjoint is the same call with P and Q exchanged.
+ *                    PCS_MDM_RADIAL: d = ||P_i - Q_j||_ord, any ord > 0 (1, 2 and +inf have fast paths, otherwise
+ *                    (sum |.|^ord)^(1/ord));  PCS_MDM_ZONAL: d = clip(<P_i, Q_j>, -1, 1), ord ignored.
+ * fp32: d and phi in fp32 with sqrtf / expf / powf; fp64: in fp64.  In both every product phi * x and every sum is
+ * carried in fp64 and rounded once at the store.  nrows > PCS_MDM_SMALL_ROWS: the row form (a 256-thread
+ * workgroup owns PCS_MDM_ROWS rows, lane = row, columns staged in LDS PCS_MDM_SLAB at a time); otherwise the column
+ * form (lane = column, one fp64 accumulator per row and lane).  The max(ceil(ncols / PCS_MDM_SLAB), 1) slabs are
+ * split into `ngroups` <= PCS_MDM_MAX_GROUPS groups of `spg` consecutive slabs, ngroups = ceil(slabs / spg) (the
+ * caller's plan).  ngroups == 1 stores directly and does not touch partials; otherwise group g writes
+ * partials[g * nrows + i] (pcs_mdm_partials_len doubles, partials_len >= that; 8-byte aligned, contents on entry:
+ * arbitrary) and a second kernel adds the groups in group order.  No atomics; the bits depend on (nrows, ncols,
+ * dim, spg, ngroups) and the data alone.  pcs_mdm_partials_len: ngroups * nrows, 0 for ngroups == 1, -1 for sizes
+ * or a group count pcs_mdm_apply rejects.
+ * PCS_EINVAL before any device call for an unknown dtype, kind or mode, parameters outside the ranges above, ord <= 0
+ * or NaN in radial mode, dim outside 1..PCS_MDM_MAX_DIM, a negative size or one of 2^31 or more, a plan that does
+ * not tile the slabs or has more than PCS_MDM_MAX_GROUPS groups, a null or misaligned or short partials when
+ * ngroups > 1, a null array, or out (or partials) overlapping an input.  nrows == 0 is a no-op; ncols == 0 writes
+ * zeros. */
+#define PCS_GREEN_MATERN 0
+#define PCS_GREEN_WENDLAND 1
+#define PCS_GREEN_SUBGAUSSIAN 2
+#define PCS_GREEN_CAUSAL_ITER 3
+#define PCS_GREEN_CAUSAL_EXP 4
+#define PCS_MDM_RADIAL 0
+#define PCS_MDM_ZONAL 1
+#define PCS_MDM_MAX_DIM 4        /* a row's point lives in registers */
+#define PCS_MDM_ROWS 64          /* rows per workgroup, row form: one lane per row */
+#define PCS_MDM_SLAB 256         /* columns staged in LDS at a time */
+#define PCS_MDM_SMALL_ROWS 16    /* at most this many rows: column form */
+#define PCS_MDM_MAX_GROUPS 1024
+int pcs_green_eval(int dtype, int kind, int k, double p0, double p1, const void* r, void* out, int64_t n,
+                   hipStream_t stream);
+int pcs_mdm_apply(int dtype, int kind, int k, double p0, double p1, int mode, double ord, int dim, const void* P,
+                  int64_t nrows, const void* Q, int64_t ncols, const void* x, void* out, int64_t spg, int64_t ngroups,
+                  void* partials, int64_t partials_len, hipStream_t stream);
+int64_t pcs_mdm_partials_len(int64_t nrows, int64_t ncols, int64_t ngroups);
+
 /* Block pooling of a C-order array of ndim in 1..3 axes (Pooling, pycsou/linop/sampling.py:394-536 ->
  * skimage.measure.block_reduce with cval = 0) and its unpooling (Pooling.adjoint, np.repeat and crop).
  * dims[ndim] is the shape of the UNPOOLED array in both calls, block[ndim] >= 1 the block sizes; the pooled

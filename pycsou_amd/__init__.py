@@ -12,7 +12,7 @@ __version__ = '0.1.0'
 
 _SUBMODULES = ('core', 'core.map', 'core.linop', 'core.functional', 'core.solver', 'linop', 'linop.base',
                'linop.conv', 'linop.diff', 'linop.sampling', 'func', 'func.base', 'func.penalty', 'func.loss', 'math',
-               'math.prox', 'opt', 'opt.proxalgs', 'opt.mcmc', 'util', 'util.misc', 'util.stats')
+               'math.prox', 'math.green', 'opt', 'opt.proxalgs', 'opt.mcmc', 'util', 'util.misc', 'util.stats')
 
 
 def install_alias(name='pycsou'):

@@ -31,6 +31,10 @@ PCS_CUMSUM_WS_MAX = 2 * 1024 * 1024 + 64 * 1024
 PCS_SPMV_LONG_ROW, PCS_SPMV_CHUNK = 4096, 4096
 # pcs_khatri_rao_*: column slab, the fused limits k n <= MAX_NK and k + n <= MAX_ROWS, most workgroups of the forward
 PCS_KR_SLAB, PCS_KR_MAX_NK, PCS_KR_MAX_ROWS, PCS_KR_MAX_GROUPS = 64, 1024, 120, 512
+# pcs_green_eval / pcs_mdm_apply: function kinds, distance modes, and the tiling of the matrix-free product
+(PCS_GREEN_MATERN, PCS_GREEN_WENDLAND, PCS_GREEN_SUBGAUSSIAN, PCS_GREEN_CAUSAL_ITER, PCS_GREEN_CAUSAL_EXP) = range(5)
+PCS_MDM_RADIAL, PCS_MDM_ZONAL = 0, 1
+PCS_MDM_MAX_DIM, PCS_MDM_ROWS, PCS_MDM_SLAB, PCS_MDM_SMALL_ROWS, PCS_MDM_MAX_GROUPS = 4, 64, 256, 16, 1024
 # pcs_cg_*: most workgroups per system, systems per launch (grid y)
 PCS_CG_MAX_BLOCKS, PCS_CG_MAX_NB = 1024, 65535
 PCS_F_NULL, PCS_F_DENOISE, PCS_F_SEPCONV, PCS_F_GRADBUF, PCS_F_CONV2D, PCS_F_CONV0 = 0, 1, 2, 3, 4, 5
@@ -132,6 +136,10 @@ _SIGS = {
     'pcs_khatri_rao_fwd': (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _c_i64,
                                     _vp]),
     'pcs_khatri_rao_adj': (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _vp]),
+    'pcs_green_eval': (_c_int, [_c_int, _c_int, _c_int, _c_dbl, _c_dbl, _vp, _vp, _c_i64, _vp]),
+    'pcs_mdm_apply': (_c_int, [_c_int, _c_int, _c_int, _c_dbl, _c_dbl, _c_int, _c_dbl, _c_int, _vp, _c_i64, _vp, _c_i64,
+                               _vp, _vp, _c_i64, _c_i64, _vp, _c_i64, _vp]),
+    'pcs_mdm_partials_len': (_c_i64, [_c_i64, _c_i64, _c_i64]),
     'pcs_pool_fwd': (_c_int, [_c_int, _vp, _vp, _c_int, _pi64, _pi64, _c_dbl, _vp]),
     'pcs_pool_adj': (_c_int, [_c_int, _vp, _vp, _c_int, _pi64, _pi64, _c_dbl, _vp]),
     'pcs_grad_fwd': (_c_int, [_c_int, _vp, _vp, _c_int, _pi64, _pdbl, _c_int, _c_int, _vp]),

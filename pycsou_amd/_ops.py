@@ -674,6 +674,74 @@ def khatri_rao_adj(A, B, Y, out=None):
     return out
 
 
+# pcs_green_eval / pcs_mdm_apply (csrc/mdm.hip)
+MDM_MAX_DIM, MDM_ROWS, MDM_SLAB, MDM_SMALL_ROWS, MDM_MAX_GROUPS = (L.PCS_MDM_MAX_DIM, L.PCS_MDM_ROWS, L.PCS_MDM_SLAB,
+                                                                   L.PCS_MDM_SMALL_ROWS, L.PCS_MDM_MAX_GROUPS)
+# Workgroups that fill the device for the plan below: 4 per CU of the 256 CUs.  A 256-thread workgroup puts one wave
+# on each SIMD of a CU; the kernels do arithmetic on registers and LDS broadcasts with no global load in the inner
+# loop, and the derivation stopped at two waves per SIMD (512 workgroups).  Measured (profiles/mdm_bench.jsonl, DESIGN
+# 5.7): the 4096 x 65536 fp32 product on 512 workgroups ran at 0.60 of the pair rate that 1024 workgroups reach, so
+# the plan asks for four waves per SIMD, which every kernel's register count admits (fp64: 3 to 4).
+MDM_FILL = 4 * 256
+MDM_MODES = {'radial': L.PCS_MDM_RADIAL, 'zonal': L.PCS_MDM_ZONAL}
+
+
+def mdm_plan(nrows, ncols):
+    """Launch plan of pcs_mdm_apply: ``(form, spg, ngroups, doubles of partials)``.  ``form`` is ``'col'`` for
+    ``nrows <= MDM_SMALL_ROWS`` and ``'row'`` otherwise.  The ``max(ceil(ncols / MDM_SLAB), 1)`` slabs go to one
+    group when the row tiles alone (``ceil(nrows / MDM_ROWS)``, 1 in the column form) number ``MDM_FILL`` or more;
+    otherwise to the fewest groups that bring tiles x groups to ``MDM_FILL``, never less than one slab per group
+    and never more than ``MDM_MAX_GROUPS`` groups.  Pure Python."""
+    nrows, ncols = int(nrows), int(ncols)
+    if nrows < 0 or ncols < 0:
+        raise ValueError('mdm_plan: negative size')
+    form = 'col' if nrows <= MDM_SMALL_ROWS else 'row'
+    tiles = 1 if form == 'col' else -(-nrows // MDM_ROWS)
+    nslabs = max(-(-ncols // MDM_SLAB), 1)
+    want = 1 if tiles >= MDM_FILL else min(-(-MDM_FILL // tiles), nslabs, MDM_MAX_GROUPS)
+    spg = -(-nslabs // want)
+    ngroups = -(-nslabs // spg)
+    return form, spg, ngroups, (ngroups * nrows if ngroups > 1 else 0)
+
+
+def green_eval(spec, r, out=None):
+    """``phi(r)`` element-wise for a float32 / float64 device tensor; ``spec``: a Green function's ``_device_spec()``."""
+    lib = L.gpu()
+    kind, k, p0, p1 = spec
+    rc = r.contiguous()
+    out = torch.empty_like(rc) if out is None else out
+    if not _dense_on(rc.device, rc, out) or out.dtype != rc.dtype or out.numel() != rc.numel():
+        raise ValueError('green_eval: r and out must be contiguous tensors of one dtype on one GPU')
+    L.check(lib.pcs_green_eval(L.dtcode(rc), int(kind), int(k), float(p0), float(p1), L.ptr(rc), L.ptr(out), rc.numel(),
+                               L.stream()), 'pcs_green_eval')
+    return out.reshape(r.shape)
+
+
+def mdm_apply(spec, mode, ord, P, Q, x, ws=None, plan=None, out=None):
+    """``out[i] = sum_j phi(d(P_i, Q_j)) x[j]`` for device point sets P (nrows, dim) and Q (ncols, dim) and a vector
+    x of ncols values, all of one dtype; ``spec`` is a Green function's ``_device_spec()``, ``mode`` ``'radial'``
+    (``ord``-norm) or ``'zonal'``.  ``plan``: ``(spg, ngroups)``, by default that of ``mdm_plan``; ``ws``: the float64
+    partials workspace of at least ``pcs_mdm_partials_len`` doubles (not needed for one group)."""
+    lib = L.gpu()
+    kind, k, p0, p1 = spec
+    if P.dim() != 2 or Q.dim() != 2 or P.shape[1] != Q.shape[1] or x.numel() != Q.shape[0] or \
+            not (P.dtype == Q.dtype == x.dtype) or not _dense_on(P.device, P, Q, x):
+        raise ValueError('mdm_apply: P (nrows, dim), Q (ncols, dim) and x (ncols) must be contiguous tensors of one '
+                         'dtype on one GPU')
+    (nrows, dim), ncols = P.shape, Q.shape[0]
+    spg, ngroups = mdm_plan(nrows, ncols)[1:3] if plan is None else plan
+    need = ngroups * nrows if ngroups > 1 else 0
+    if need and (ws is None or ws.dtype != torch.float64 or ws.numel() < need or not _dense_on(P.device, ws)):
+        raise ValueError(f'mdm_apply: the plan needs a float64 workspace of {need} doubles on {P.device}')
+    out = torch.empty(nrows, dtype=P.dtype, device=P.device) if out is None else out
+    if out.dtype != P.dtype or out.numel() != nrows or not _dense_on(P.device, out):
+        raise ValueError(f'mdm_apply: out must be a contiguous {P.dtype} tensor of {nrows} values on {P.device}')
+    L.check(lib.pcs_mdm_apply(L.dtcode(P), int(kind), int(k), float(p0), float(p1), MDM_MODES[mode], float(ord), dim,
+                              L.ptr(P), nrows, L.ptr(Q), ncols, L.ptr(x), L.ptr(out), int(spg), int(ngroups),
+                              L.ptr(ws) if need else None, ws.numel() if need else 0, L.stream()), 'pcs_mdm_apply')
+    return out
+
+
 def _pool_call(fn, name, x, dims, block, scale, n_out):
     dims, block = [int(d) for d in dims], [int(b) for b in block]
     if len(dims) != len(block) or not 1 <= len(dims) <= 3:

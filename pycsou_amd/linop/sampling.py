@@ -10,7 +10,8 @@ indices and the inverse map once, on the host; forward and adjoint are the gathe
 (``csrc/pool.hip``).  ``NNSampling`` (``sampling.py:539-687``), ``GeneralisedVandermonde``
 (``sampling.py:690-769``) and ``MappedDistanceMatrix`` (``sampling.py:772-1058``) do their set-up (k-d trees,
 Python callables, matrix assembly) once on the host and are then a gather, a dense matrix or a CSR matrix
-on the device (``pcs_csr_spmv``, ``csrc/spmv.hip``).
+on the device (``pcs_csr_spmv``, ``csrc/spmv.hip``).  A ``'dask'`` ``MappedDistanceMatrix`` of one of the Green
+functions of ``pycsou_amd.math.green`` assembles nothing: it is matrix-free on ``pcs_mdm_apply`` (``csrc/mdm.hip``).
 """
 
 import numpy as np
@@ -294,8 +295,14 @@ class MappedDistanceMatrix(ExplicitLinearOperator):
       is applied in one vectorised call over all retained pairs, and the result is stored as a CSR matrix
       with sorted indices: a sparse operator on ``pcs_csr_spmv``.  ``n_jobs``, ``verbose`` and
       ``joblib_backend`` are accepted and unused.
-    * ``'dask'`` (the default): dask is not a dependency of this package; the dense matrix is built instead and
-      ``is_dask`` stays ``False`` (``chunks`` is accepted and unused)."""
+    * ``'dask'`` (the default), the reference's memory-lean form.  With ``function`` one of the Green functions of
+      ``pycsou_amd.math.green``, points of at most ``PCS_MDM_MAX_DIM`` coordinates and a float32 / float64 ``dtype``
+      the operator is matrix-free (``matrix_free = True``, ``mat = None``, ``is_dask = True``): the two point sets
+      are uploaded once per dtype and ``pcs_mdm_apply`` (``csrc/mdm.hip``) evaluates ``phi(d(z_l, x_k))`` in
+      registers, forward and adjoint being the same kernel with the point sets exchanged -- O(L + K) memory.
+      ``max_distance``, ``eps`` and ``chunks`` are ignored, as the reference's dask path ignores them.  With any
+      other callable (a lambda cannot run on the device), a higher dimension or another dtype, dask not being a
+      dependency of this package, the dense matrix is built instead and ``is_dask`` stays ``False``."""
 
     def __init__(self, samples1, function, samples2=None, mode='radial', max_distance=None, dtype=np.float64,
                  chunks='auto', operator_type='dask', verbose=True, n_jobs=-1, joblib_backend='loky', ord=2., eps=0):
@@ -322,6 +329,15 @@ class MappedDistanceMatrix(ExplicitLinearOperator):
         self.joblib_backend = joblib_backend
         self.ord = ord
         self.eps = eps
+        self.matrix_free = self._device_function_ok()
+        if self.matrix_free:
+            LinearOperator.__init__(self, shape=(self.samples1.shape[0], self.samples2.shape[0]), dtype=dtype,
+                                    is_explicit=True, is_dense=False, is_sparse=False, is_dask=True,
+                                    is_symmetric=symmetric)
+            self.mat = None
+            self._spec = function._device_spec()
+            self._points, self._partials = {}, {}
+            return
         if operator_type == 'sparse':
             self.is_symmetric = symmetric       # get_sparse_mdm shares the tree of a symmetric operator
             mat = self.get_sparse_mdm()
@@ -330,6 +346,55 @@ class MappedDistanceMatrix(ExplicitLinearOperator):
         else:
             raise ValueError(f'Unsupported operator type {operator_type}.')
         super().__init__(array=mat, is_symmetric=symmetric)
+
+    def _device_function_ok(self):
+        """Whether the operator is matrix-free: the 'dask' type, a Green function of this package (recognised by
+        class, nothing else) whose parameters have a device form, points the kernels hold in registers, a dtype they compute in."""
+        from ..math.green import GREEN_CLASSES
+        try:
+            dt = np.dtype(self.dtype)
+        except TypeError:
+            return False
+        return (self.operator_type == 'dask' and isinstance(self.function, GREEN_CLASSES)
+                and self.function._device_ok()
+                and self.samples1.ndim == 2 and self.samples2.ndim == 2
+                and 1 <= self.samples1.shape[1] == self.samples2.shape[1] <= O.MDM_MAX_DIM
+                and dt in (np.dtype(np.float32), np.dtype(np.float64)))
+
+    def _pts(self, dtype):
+        """The two point sets on the device in ``dtype`` (one tensor when the operator is symmetric)."""
+        p = self._points.get(dtype)
+        if p is None:
+            up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(  # noqa: E731
+                device=O.device(), dtype=dtype).contiguous()
+            p1 = up(self.samples1)
+            p = self._points[dtype] = (p1, p1 if self.samples2 is self.samples1 else up(self.samples2))
+        return p
+
+    def _mdm(self, t, adjoint):
+        p1, p2 = self._pts(t.dtype)
+        P, Q = (p2, p1) if adjoint else (p1, p2)
+        _, spg, ngroups, need = O.mdm_plan(P.shape[0], Q.shape[0])
+        ws = self._partials.get(adjoint)
+        if need and (ws is None or ws.numel() != need or ws.device != t.device):
+            ws = self._partials[adjoint] = torch.empty(need, dtype=torch.float64, device=t.device)
+        return O.mdm_apply(self._spec, self.mode, self.ord, P, Q, t.contiguous(), ws, (spg, ngroups))
+
+    def _apply(self, t):
+        return self._mdm(t, False) if self.matrix_free else super()._apply(t)
+
+    def _adj(self, t):
+        return self._mdm(t, True) if self.matrix_free else super()._adj(t)
+
+    def _apply_cols(self, T, axis, adjoint=False):
+        if self.matrix_free:       # the generic loop over the lines on the device
+            return LinearOperator._apply_cols(self, T, axis, adjoint)
+        return super()._apply_cols(T, axis, adjoint)
+
+    def _apply_cols_acc(self, T, axis, adjoint, acc):
+        if self.matrix_free:
+            return LinearOperator._apply_cols_acc(self, T, axis, adjoint, acc)
+        return super()._apply_cols_acc(T, axis, adjoint, acc)
 
     def _distances(self, a, b):
         if self.mode == 'radial':
