@@ -84,6 +84,10 @@ __device__ __forceinline__ T clip1(T v) {
   return v > T(1) ? T(1) : (v < T(-1) ? T(-1) : v);
 }
 
+// One rounding, spelled out: where a kernel's instantiations must give the same bits (stencil.hpp)
+__device__ __forceinline__ float pcs_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double pcs_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
 // ---------------------------------------------------------------- reductions
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

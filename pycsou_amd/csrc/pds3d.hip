@@ -463,9 +463,9 @@ __global__ __launch_bounds__(FK == PCS_F_CONV0 ? 2 * K3<T>::NT : K3<T>::NT, FK =
         const T a0 = P.unit[0] ? d0 : d0 * P.inv_step[0];
         const T a1 = P.unit[1] ? d1 : d1 * P.inv_step[1];
         const T a2 = P.unit[2] ? d2 : d2 * P.inv_step[2];
-        const T xt = prox_g((xv - P.tau * gf) - P.tau * ((a0 + a1) + a2), gk, P.seg_a, P.seg_b);
-        uo.v[m] = (in && cm) ? (T(2) * xt - xv) : T(0);
-        const T xnew = P.rho * xt + P.omr * xv;
+        const T xt = primal_prox(grad_step(xv, gf, P), (a0 + a1) + a2, gk, P);
+        uo.v[m] = (in && cm) ? reflect(xt, xv) : T(0);
+        const T xnew = relax<false>(xt, xv, P);
         xo.v[m] = xnew;
         const T dx = xv - xnew;
         sdx += cm ? dx * dx : T(0);
@@ -505,23 +505,22 @@ __global__ __launch_bounds__(FK == PCS_F_CONV0 ? 2 * K3<T>::NT : K3<T>::NT, FK =
         const T k0 = P.unit[0] ? d0 : d0 * P.inv_step[0];
         const T k1 = P.unit[1] ? d1 : d1 * P.inv_step[1];
         const T k2 = P.unit[2] ? d2 : d2 * P.inv_step[2];
-        const T w0 = zv0.v[m] + P.sigma * k0, w1 = zv1.v[m] + P.sigma * k1, w2 = zv2.v[m] + P.sigma * k2;
-        const T v0 = w0 * P.inv_sigma, v1 = w1 * P.inv_sigma, v2 = w2 * P.inv_sigma;
+        const T w0 = dual_arg(zv0.v[m], k0, P), w1 = dual_arg(zv1.v[m], k1, P), w2 = dual_arg(zv2.v[m], k2, P);
+        const T v0 = dual_scaled(w0, P), v1 = dual_scaled(w1, P), v2 = dual_scaled(w2, P);
         T t0, t1, t2;
-        if (hk == PCS_H_L21) {  // w - sigma * (max(1 - t/||v||, 0) v), penalty.py:551-557
-          T f = T(1) - P.t_h * fast_rsqrt((v0 * v0 + v1 * v1) + v2 * v2);
-          f = f > T(0) ? f : T(0);
-          t0 = w0 - P.sigma * (f * v0);
-          t1 = w1 - P.sigma * (f * v1);
-          t2 = w2 - P.sigma * (f * v2);
-        } else {  // w - sigma * (v - t*clip(v/t)), func/base.py:239-240
-          t0 = w0 - P.sigma * (v0 - P.t_h * clip1(v0 * P.inv_t_h));
-          t1 = w1 - P.sigma * (v1 - P.t_h * clip1(v1 * P.inv_t_h));
-          t2 = w2 - P.sigma * (v2 - P.t_h * clip1(v2 * P.inv_t_h));
+        if (hk == PCS_H_L21) {
+          const T f = l21_shrink(norm2<false>(v0, v1, v2), P);
+          t0 = fenchel_l21(w0, v0, f, P);
+          t1 = fenchel_l21(w1, v1, f, P);
+          t2 = fenchel_l21(w2, v2, f, P);
+        } else {
+          t0 = fenchel_l1(w0, v0, P);
+          t1 = fenchel_l1(w1, v1, P);
+          t2 = fenchel_l1(w2, v2, P);
         }
-        o0.v[m] = P.rho * t0 + P.omr * zv0.v[m];
-        o1.v[m] = P.rho * t1 + P.omr * zv1.v[m];
-        o2.v[m] = P.rho * t2 + P.omr * zv2.v[m];
+        o0.v[m] = relax<false>(t0, zv0.v[m], P);
+        o1.v[m] = relax<false>(t1, zv1.v[m], P);
+        o2.v[m] = relax<false>(t2, zv2.v[m], P);
         const T e0 = zv0.v[m] - o0.v[m], e1 = zv1.v[m] - o1.v[m], e2 = zv2.v[m] - o2.v[m];
         sdz += cm ? (e0 * e0 + e1 * e1) + e2 * e2 : T(0);
         sz += cm ? (zv0.v[m] * zv0.v[m] + zv1.v[m] * zv1.v[m]) + zv2.v[m] * zv2.v[m] : T(0);
@@ -772,9 +771,10 @@ __global__ __launch_bounds__(k3g_nt<T>(), PCS_3DG_MINB) void k_pds3d_gen(const T
             if constexpr (FK == PCS_F_NULL) gf = T(0);
             else if constexpr (FK == PCS_F_DENOISE) gf = xv - gv4[k].v[m];
             else gf = gv4[k].v[m];
-            const T xt = prox_g((xv - P.tau * gf) - P.tau * kt, gk, P.seg_a, P.seg_b);
-            uo.v[m] = in ? (T(2) * xt - xv) : T(0);
-            const T xnew = pcs_fma(P.rho, xt, P.omr * xv);
+            const T xt = primal_prox(grad_step(xv, gf, P), kt, gk, P);
+            const T ur = reflect(xt, xv);
+            uo.v[m] = in ? ur : T(0);
+            const T xnew = relax<true>(xt, xv, P);
             xo.v[m] = xnew;
             const T dx = xv - xnew;
             sdx += in ? dx * dx : T(0);
@@ -827,23 +827,22 @@ __global__ __launch_bounds__(k3g_nt<T>(), PCS_3DG_MINB) void k_pds3d_gen(const T
             const T k0 = sw_d1_fwd<KK, I0>(w0, gq, v.n0, P.inv_step[0], edge);
             const T k1 = sw_d1_fwd<KK, I1>(w1, i1z, v.n1, P.inv_step[1], edge);
             const T k2 = sw_d1_fwd<KK, I2>(w2, i2, v.n2, P.inv_step[2], edge);
-            const T w0v = zv0.v[m] + P.sigma * k0, w1v = zv1.v[m] + P.sigma * k1, w2v = zv2.v[m] + P.sigma * k2;
-            const T v0 = w0v * P.inv_sigma, v1 = w1v * P.inv_sigma, v2 = w2v * P.inv_sigma;
+            const T w0v = dual_arg(zv0.v[m], k0, P), w1v = dual_arg(zv1.v[m], k1, P), w2v = dual_arg(zv2.v[m], k2, P);
+            const T v0 = dual_scaled(w0v, P), v1 = dual_scaled(w1v, P), v2 = dual_scaled(w2v, P);
             T t0, t1, t2;
-            if (hk == PCS_H_L21) {  // w - sigma * (max(1 - t/||v||, 0) v), penalty.py:551-557
-              T f = T(1) - P.t_h * fast_rsqrt(pcs_fma(v0, v0, pcs_fma(v1, v1, v2 * v2)));
-              f = f > T(0) ? f : T(0);
-              t0 = w0v - P.sigma * (f * v0);
-              t1 = w1v - P.sigma * (f * v1);
-              t2 = w2v - P.sigma * (f * v2);
-            } else {  // w - sigma * (v - t*clip(v/t)), func/base.py:239-240
-              t0 = w0v - P.sigma * (v0 - P.t_h * clip1(v0 * P.inv_t_h));
-              t1 = w1v - P.sigma * (v1 - P.t_h * clip1(v1 * P.inv_t_h));
-              t2 = w2v - P.sigma * (v2 - P.t_h * clip1(v2 * P.inv_t_h));
+            if (hk == PCS_H_L21) {
+              const T f = l21_shrink(norm2<true>(v0, v1, v2), P);
+              t0 = fenchel_l21(w0v, v0, f, P);
+              t1 = fenchel_l21(w1v, v1, f, P);
+              t2 = fenchel_l21(w2v, v2, f, P);
+            } else {
+              t0 = fenchel_l1(w0v, v0, P);
+              t1 = fenchel_l1(w1v, v1, P);
+              t2 = fenchel_l1(w2v, v2, P);
             }
-            o0.v[m] = pcs_fma(P.rho, t0, P.omr * zv0.v[m]);
-            o1.v[m] = pcs_fma(P.rho, t1, P.omr * zv1.v[m]);
-            o2.v[m] = pcs_fma(P.rho, t2, P.omr * zv2.v[m]);
+            o0.v[m] = relax<true>(t0, zv0.v[m], P);
+            o1.v[m] = relax<true>(t1, zv1.v[m], P);
+            o2.v[m] = relax<true>(t2, zv2.v[m], P);
             const T e0 = zv0.v[m] - o0.v[m], e1 = zv1.v[m] - o1.v[m], e2 = zv2.v[m] - o2.v[m];
             sdz += cm ? pcs_fma(e0, e0, pcs_fma(e1, e1, e2 * e2)) : T(0);
             sz += cm ? pcs_fma(zv0.v[m], zv0.v[m], pcs_fma(zv1.v[m], zv1.v[m], zv2.v[m] * zv2.v[m])) : T(0);

@@ -215,9 +215,9 @@ __device__ __forceinline__ void gen_tile(const T* __restrict__ x, T* __restrict_
           T kt;
           if constexpr (INT) kt = gen_kt_int<T, KK>(Z, ZS, lz + m, P);
           else kt = gen_kt<T, KK>(Z, ZS, lz + m, i0, i1, n0, n1, P, edge);
-          const T xt = prox_g((xv - P.tau * gf) - P.tau * kt, gk, P.seg_a, P.seg_b);
-          u = T(2) * xt - xv;
-          xnew = P.rho * xt + P.omr * xv;
+          const T xt = primal_prox(grad_step(xv, gf, P), kt, gk, P);
+          u = reflect(xt, xv);
+          xnew = relax<false>(xt, xv, P);
         }
         const T dx = xv - xnew;
         sdx += (in && i1 < n1) ? dx * dx : T(0);
@@ -262,22 +262,21 @@ __device__ __forceinline__ void gen_tile(const T* __restrict__ x, T* __restrict_
 #pragma unroll
           for (int d = 0; d < D; ++d) {
             zv[d] = Z[d * ZS + lz + m];
-            w[d] = zv[d] + P.sigma * ku[d];
-            v[d] = w[d] * P.inv_sigma;
+            w[d] = dual_arg(zv[d], ku[d], P);
+            v[d] = dual_scaled(w[d], P);
           }
-          if (D == 2 && hk == PCS_H_L21) {  // w - sigma * (max(1 - t/||v||, 0) v), penalty.py:551-557
-            T f = T(1) - P.t_h * fast_rsqrt(v[0] * v[0] + v[D - 1] * v[D - 1]);
-            f = f > T(0) ? f : T(0);
+          if (D == 2 && hk == PCS_H_L21) {
+            const T f = l21_shrink(norm2<false>(v[0], v[D - 1]), P);
 #pragma unroll
-            for (int d = 0; d < D; ++d) zt[d] = w[d] - P.sigma * (f * v[d]);
-          } else {  // w - sigma * (v - t*clip(v/t)), func/base.py:239-240
+            for (int d = 0; d < D; ++d) zt[d] = fenchel_l21(w[d], v[d], f, P);
+          } else {
 #pragma unroll
-            for (int d = 0; d < D; ++d) zt[d] = w[d] - P.sigma * (v[d] - P.t_h * clip1(v[d] * P.inv_t_h));
+            for (int d = 0; d < D; ++d) zt[d] = fenchel_l1(w[d], v[d], P);
           }
           const bool cm = INT || i1 < n1;
 #pragma unroll
           for (int d = 0; d < D; ++d) {
-            o[d].v[m] = P.rho * zt[d] + P.omr * zv[d];
+            o[d].v[m] = relax<false>(zt[d], zv[d], P);
             const T ed = zv[d] - o[d].v[m];
             sdz += cm ? ed * ed : T(0);
             sz += cm ? zv[d] * zv[d] : T(0);

@@ -550,12 +550,12 @@ __device__ __forceinline__ void march_task(const T* __restrict__ x, T* __restric
       T d0 = r_first ? T(0) : (m < 4 ? za.v[m] : zae);
       if (!r_last) d0 -= (m < 4 ? zb.v[m] : zbe);
       const T d1 = zl - ((m == 3 && clast) ? T(0) : zr);
-      const T xt = prox_g((xv - P.tau * gd) - P.tau * (d0 * P.inv_step0 + d1 * P.inv_step1), gk, P.seg_a, P.seg_b);
+      const T xt = primal_prox(grad_step(xv, gd, P), d0 * P.inv_step0 + d1 * P.inv_step1, gk, P);
       const bool in = rrow && (m < 4 ? cin : cin_e);
-      const T u = in ? (T(2) * xt - xv) : T(0);
+      const T u = in ? reflect(xt, xv) : T(0);
       if (m < 4) {
         uo.v[m] = u;
-        const T xnew = P.rho * xt + P.omr * xv;
+        const T xnew = relax<false>(xt, xv, P);
         xo.v[m] = xnew;
         const T dx = xv - xnew;
         sdx += dx * dx;
@@ -609,20 +609,12 @@ __device__ __forceinline__ void march_task(const T* __restrict__ x, T* __restric
       const T uright = (m < 3) ? uc.v[m + 1] : une;
       const T d0 = r_last ? T(0) : (ud.v[m] - uc.v[m]);
       const T d1 = (m == 3 && clast) ? T(0) : (uright - uc.v[m]);
-      const T w0v = zv0.v[m] + P.sigma * (d0 * P.inv_step0), w1v = zv1.v[m] + P.sigma * (d1 * P.inv_step1);
-      const T v0 = w0v * P.inv_sigma, v1 = w1v * P.inv_sigma;
-      T zt0, zt1;
-      if (HK == PCS_H_L21) {  // w - sigma * (max(1 - t/||v||, 0) v), penalty.py:551-557
-        T f = T(1) - P.t_h * fast_rsqrt(v0 * v0 + v1 * v1);
-        f = f > T(0) ? f : T(0);
-        zt0 = w0v - P.sigma * (f * v0);
-        zt1 = w1v - P.sigma * (f * v1);
-      } else {  // w - sigma * (v - t*clip(v/t)), func/base.py:239-240
-        zt0 = w0v - P.sigma * (v0 - P.t_h * clip1(v0 * P.inv_t_h));
-        zt1 = w1v - P.sigma * (v1 - P.t_h * clip1(v1 * P.inv_t_h));
-      }
-      o0.v[m] = P.rho * zt0 + P.omr * zv0.v[m];
-      o1.v[m] = P.rho * zt1 + P.omr * zv1.v[m];
+      const T zv[2] = {zv0.v[m], zv1.v[m]};
+      const T w[2] = {dual_arg(zv[0], d0 * P.inv_step0, P), dual_arg(zv[1], d1 * P.inv_step1, P)};
+      T zt[2];
+      fenchel_w<2, Fenchel::Literal, false>(HK, w, P, zt);
+      o0.v[m] = relax<false>(zt[0], zv[0], P);
+      o1.v[m] = relax<false>(zt[1], zv[1], P);
       const T e0 = zv0.v[m] - o0.v[m], e1 = zv1.v[m] - o1.v[m];
       sdz += e0 * e0 + e1 * e1;
       sz += zv0.v[m] * zv0.v[m] + zv1.v[m] * zv1.v[m];

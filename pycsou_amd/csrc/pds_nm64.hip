@@ -279,9 +279,9 @@ __device__ __forceinline__ void nm64_task(const double* __restrict__ x, double* 
         const T kt = pcs_fma(sw_d1_adj<KK, I0>(w0, gr, n0, edge), P.inv_step0,
                              sw_d1_adj<KK, I1>(w1, c, n1, edge) * P.inv_step1);
         const T xvm = xv2.v[m];
-        const T xt = prox_g((xvm - P.tau * gv[r][m]) - P.tau * kt, gk, P.seg_a, P.seg_b);
-        uo.v[m] = (rin && c_in) ? (T(2) * xt - xvm) : T(0);
-        const T xnew = pcs_fma(P.rho, xt, P.omr * xvm);
+        const T xt = primal_prox(grad_step(xvm, gv[r][m], P), kt, gk, P);
+        uo.v[m] = (rin && c_in) ? reflect(xt, xvm) : T(0);
+        const T xnew = relax<true>(xt, xvm, P);
         xo.v[m] = xnew;
         const T dx = xvm - xnew;
         sdx += dx * dx;
@@ -326,20 +326,12 @@ __device__ __forceinline__ void nm64_task(const double* __restrict__ x, double* 
         const T w1[5] = {T(0), uc[1 + m], uc[2 + m], uc[3 + m], T(0)};  // columns c - 1 .. c + 1
         const T ku0 = sw_d1_fwd<KK, I0>(w0, gr, n0, P.inv_step0, edge);
         const T ku1 = sw_d1_fwd<KK, I1>(w1, c, n1, P.inv_step1, edge);
-        const T wz0 = zv0.v[m] + P.sigma * ku0, wz1 = zv1.v[m] + P.sigma * ku1;
-        const T q0 = wz0 * P.inv_sigma, q1 = wz1 * P.inv_sigma;
-        T zt0, zt1;
-        if constexpr (HK == PCS_H_L21) {  // w - sigma * (max(1 - t/||v||, 0) v), penalty.py:551-557
-          T f = T(1) - P.t_h * fast_rsqrt(pcs_fma(q0, q0, q1 * q1));
-          f = f > T(0) ? f : T(0);
-          zt0 = wz0 - P.sigma * (f * q0);
-          zt1 = wz1 - P.sigma * (f * q1);
-        } else {  // w - sigma * (v - t*clip(v/t)), func/base.py:239-240
-          zt0 = wz0 - P.sigma * (q0 - P.t_h * clip1(q0 * P.inv_t_h));
-          zt1 = wz1 - P.sigma * (q1 - P.t_h * clip1(q1 * P.inv_t_h));
-        }
-        o0.v[m] = pcs_fma(P.rho, zt0, P.omr * zv0.v[m]);
-        o1.v[m] = pcs_fma(P.rho, zt1, P.omr * zv1.v[m]);
+        const T zv[2] = {zv0.v[m], zv1.v[m]};
+        const T w[2] = {dual_arg(zv[0], ku0, P), dual_arg(zv[1], ku1, P)};
+        T zp[2];  // (zt is this kernel's z tile reader)
+        fenchel_w<2, Fenchel::Literal, true>(HK, w, P, zp);
+        o0.v[m] = relax<true>(zp[0], zv[0], P);
+        o1.v[m] = relax<true>(zp[1], zv[1], P);
         const T e0 = zv0.v[m] - o0.v[m], e1 = zv1.v[m] - o1.v[m];
         sdz += e0 * e0;
         sz += zv0.v[m] * zv0.v[m];

@@ -460,7 +460,7 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
         T d0 = r_first ? T(0) : za_;
         if (!r_last) d0 -= zb_;
         const T d1 = zl - (last_col ? T(0) : zr);
-        return prox_g((xv - P.tau * gd) - P.tau * (d0 * P.inv_step0 + d1 * P.inv_step1), gk, P.seg_a, P.seg_b);
+        return primal_prox(grad_step(xv, gd, P), d0 * P.inv_step0 + d1 * P.inv_step1, gk, P);
       };
       G4<T> uo, xo;
       T sdx = T(0), sx = T(0);
@@ -469,8 +469,8 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
         const T xv = xv4.v[m];
         const T xt = xt_of(g.v[m] - bv.v[m], xv, za.v[m], zb.v[m], (m == 0) ? z1a.v[3] : z1b.v[m - 1], z1b.v[m],
                            m == 3 && clast);
-        uo.v[m] = (rrow && cin) ? (T(2) * xt - xv) : T(0);
-        const T xnew = P.rho * xt + P.omr * xv;
+        uo.v[m] = (rrow && cin) ? reflect(xt, xv) : T(0);
+        const T xnew = relax<false>(xt, xv, P);
         xo.v[m] = xnew;
         const T dx = xv - xnew;
         sdx += dx * dx;
@@ -509,12 +509,11 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
         T d0 = f_first ? T(0) : Z0[fur * WZ0 + TW];
         if (!f_last) d0 -= Z0[(fur + 1) * WZ0 + TW];
         const T d1 = Z1[(fur + 1) * WZ1 + TW + 3] - Z1[(fur + 1) * WZ1 + TW + 4];
-        const T xt = prox_g((xe - P.tau * (pg - b5)) - P.tau * (d0 * P.inv_step0 + d1 * P.inv_step1), gk, P.seg_a,
-                            P.seg_b);
+        const T xt = primal_prox(grad_step(xe, pg - b5, P), d0 * P.inv_step0 + d1 * P.inv_step1, gk, P);
         int fslot = fur + 1 + ub;
         fslot = fslot >= UR ? fslot - UR : fslot;
         const bool frow = fgr < n0 && flr <= s.rows;
-        if (fsub == 0) U[fslot * WU + TW] = (frow && c0 + TW < n1) ? (T(2) * xt - xe) : T(0);
+        if (fsub == 0) U[fslot * WU + TW] = (frow && c0 + TW < n1) ? reflect(xt, xe) : T(0);
       }
 #else
       if (!(PCS_NMG_ABL & 4) && ug == GG - 1) {  // the strip's 65th column c0 + 64 (never the image's last: n1 % 4 == 0)
@@ -534,7 +533,7 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
         const T xe = lds1(XR + (lr & 31) * WX + XL + TW);
         const T xt = xt_of(g4 - b5, xe, lds1(Z0 + ui * WZ0 + TW), lds1(Z0 + (ui + 1) * WZ0 + TW), z1b.v[3],
                            lds1(Z1 + (ui + 1) * WZ1 + TW + 4), false);
-        urow[4] = (rrow && ucg + 4 < n1) ? (T(2) * xt - xe) : T(0);
+        urow[4] = (rrow && ucg + 4 < n1) ? reflect(xt, xe) : T(0);
       }
 #endif
     } else {  // backward / centred K: K^T z from z rows lr - 1 .. lr + 1, columns c - 1 .. c + 1
@@ -555,7 +554,7 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
         constexpr bool I1 = decltype(intc)::value || (PCS_NMG_ABL & 2);
         const T kt = pcs_fma(sw_d1_adj<KK, I0>(w0, gr, n0, edge), P.inv_step0,
                              sw_d1_adj<KK, I1>(w1, i1, n1, edge) * P.inv_step1);
-        return prox_g((xv - P.tau * gd) - P.tau * kt, gk, P.seg_a, P.seg_b);
+        return primal_prox(grad_step(xv, gd, P), kt, gk, P);
       };
       G4<T> uo, xo;
       T sdx = T(0), sx = T(0);
@@ -566,8 +565,8 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
           const T w0[5] = {T(0), za.v[m], zb.v[m], zc.v[m], T(0)};
           const T w1[5] = {T(0), zh[m], zh[m + 1], zh[m + 2], T(0)};
           const T xt = xt_of(intr, intc, g.v[m] - bv.v[m], xv, w0, w1, ucg + m);
-          uo.v[m] = (rrow && cin) ? (T(2) * xt - xv) : T(0);
-          const T xnew = pcs_fma(P.rho, xt, P.omr * xv);
+          uo.v[m] = (rrow && cin) ? reflect(xt, xv) : T(0);
+          const T xnew = relax<true>(xt, xv, P);
           xo.v[m] = xnew;
           const T dx = xv - xnew;
           sdx += dx * dx;
@@ -618,11 +617,11 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
         // K^T z on the extra column's row (egr) through xt_of's row index: recompute with egr
         const T kt = pcs_fma(sw_d1_adj<KK, false>(w0, egr, n0, edge), P.inv_step0,
                              sw_d1_adj<KK, false>(w1, ecol, n1, edge) * P.inv_step1);
-        const T xt = prox_g((xe - P.tau * (part_g - bm1)) - P.tau * kt, gk, P.seg_a, P.seg_b);
+        const T xt = primal_prox(grad_step(xe, part_g - bm1, P), kt, gk, P);
         int eslot = eur + 1 + ub;
         eslot = eslot >= UR ? eslot - UR : eslot;
         const bool erow = (unsigned)egr < (unsigned)n0 && elr <= s.rows;
-        if (esub == 0) U[eslot * WU + ets] = (erow && (unsigned)ecol < (unsigned)n1) ? (T(2) * xt - xe) : T(0);
+        if (esub == 0) U[eslot * WU + ets] = (erow && (unsigned)ecol < (unsigned)n1) ? reflect(xt, xe) : T(0);
       }
     }
   };
@@ -646,19 +645,12 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
       const T uright = (m < 3) ? uc.v[m + 1] : une;
       const T d0 = r_last ? T(0) : (ud.v[m] - uc.v[m]);
       const T d1 = (m == 3 && clast) ? T(0) : (uright - uc.v[m]);
-      const T w0v = zv0.v[m] + P.sigma * (d0 * P.inv_step0), w1v = zv1.v[m] + P.sigma * (d1 * P.inv_step1);
-      T zt0, zt1;
-      if (HK == PCS_H_L21) {
-        // w - sigma prox_{L21, t}(w / sigma) (penalty.py:551-557, t = lam / sigma) = w min(1, lam / ||w||)
-        const T sc = fminf(T(1), P.lam * fast_rsqrt(w0v * w0v + w1v * w1v));
-        zt0 = w0v * sc;
-        zt1 = w1v * sc;
-      } else {  // w - sigma (v - t clip(v / t)), v = w / sigma (func/base.py:239-240) = clip(w, -lam, lam)
-        zt0 = fminf(fmaxf(w0v, -P.lam), P.lam);
-        zt1 = fminf(fmaxf(w1v, -P.lam), P.lam);
-      }
-      o0.v[m] = P.rho * zt0 + P.omr * zv0.v[m];
-      o1.v[m] = P.rho * zt1 + P.omr * zv1.v[m];
+      const T zv[2] = {zv0.v[m], zv1.v[m]};
+      const T w[2] = {dual_arg(zv[0], d0 * P.inv_step0, P), dual_arg(zv[1], d1 * P.inv_step1, P)};
+      T zt[2];
+      fenchel_w<2, Fenchel::Direct, false>(HK, w, P, zt);
+      o0.v[m] = relax<false>(zt[0], zv[0], P);
+      o1.v[m] = relax<false>(zt[1], zv[1], P);
       const T e0 = zv0.v[m] - o0.v[m], e1 = zv1.v[m] - o1.v[m];
       sdz += e0 * e0 + e1 * e1;
       sz += zv0.v[m] * zv0.v[m] + zv1.v[m] * zv1.v[m];
@@ -699,18 +691,12 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
         const T w1[5] = {T(0), uh[m], uh[m + 1], uh[m + 2], T(0)};
         const T k0 = sw_d1_fwd<KK, I0>(w0, gr, n0, P.inv_step0, edge);
         const T k1 = sw_d1_fwd<KK, I1>(w1, ucg + m, n1, P.inv_step1, edge);
-        const T w0v = zv0.v[m] + P.sigma * k0, w1v = zv1.v[m] + P.sigma * k1;
-        T zt0, zt1;
-        if (HK == PCS_H_L21) {  // w min(1, lam / ||w||), as p6f
-          const T sc = fminf(T(1), P.lam * fast_rsqrt(pcs_fma(w0v, w0v, w1v * w1v)));
-          zt0 = w0v * sc;
-          zt1 = w1v * sc;
-        } else {
-          zt0 = fminf(fmaxf(w0v, -P.lam), P.lam);
-          zt1 = fminf(fmaxf(w1v, -P.lam), P.lam);
-        }
-        o0.v[m] = pcs_fma(P.rho, zt0, P.omr * zv0.v[m]);
-        o1.v[m] = pcs_fma(P.rho, zt1, P.omr * zv1.v[m]);
+        const T zv[2] = {zv0.v[m], zv1.v[m]};
+        const T w[2] = {dual_arg(zv[0], k0, P), dual_arg(zv[1], k1, P)};
+        T zt[2];
+        fenchel_w<2, Fenchel::Direct, true>(HK, w, P, zt);
+        o0.v[m] = relax<true>(zt[0], zv[0], P);
+        o1.v[m] = relax<true>(zt[1], zv[1], P);
         const T e0 = zv0.v[m] - o0.v[m], e1 = zv1.v[m] - o1.v[m];
         sdz += pcs_fma(e0, e0, e1 * e1);
         sz += pcs_fma(zv0.v[m], zv0.v[m], zv1.v[m] * zv1.v[m]);
@@ -810,12 +796,11 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
       T d0 = r_first ? T(0) : z0c[o];
       if (!r_last) d0 -= z0c[o + 1];
       const T d1 = zl - (cclast ? T(0) : zc);
-      const T xt = prox_g((xv - P.tau * (g[o] - bc[o])) - P.tau * (d0 * P.inv_step0 + d1 * P.inv_step1), gk,
-                          P.seg_a, P.seg_b);
+      const T xt = primal_prox(grad_step(xv, g[o] - bc[o], P), d0 * P.inv_step0 + d1 * P.inv_step1, gk, P);
       int slot = 4 * wv + o + 1 + ub;
       slot = slot >= UR ? slot - UR : slot;
-      U[slot * WU + lane] = (rrow && ccin) ? (T(2) * xt - xv) : T(0);
-      const T xnew = P.rho * xt + P.omr * xv;
+      U[slot * WU + lane] = (rrow && ccin) ? reflect(xt, xv) : T(0);
+      const T xnew = relax<false>(xt, xv, P);
       bstore1<PCS_NM_SAUX>(rxn, (own ? (uint32_t)(lr + s.hx) * pitch : kOOB) + co_cc, xnew);
       if (own) {
         const T dx = xv - xnew;
@@ -846,12 +831,11 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
       T d0 = f_first ? T(0) : Z0[fur * WZ0 + TW];
       if (!f_last) d0 -= Z0[(fur + 1) * WZ0 + TW];
       const T d1 = Z1[(fur + 1) * WZ1 + TW + 3] - Z1[(fur + 1) * WZ1 + TW + 4];
-      const T xt = prox_g((xe - P.tau * (pg - b5)) - P.tau * (d0 * P.inv_step0 + d1 * P.inv_step1), gk, P.seg_a,
-                          P.seg_b);
+      const T xt = primal_prox(grad_step(xe, pg - b5, P), d0 * P.inv_step0 + d1 * P.inv_step1, gk, P);
       int fslot = fur + 1 + ub;
       fslot = fslot >= UR ? fslot - UR : fslot;
       const bool frow = fgr < n0 && flr <= s.rows;
-      if (fsub == 0) U[fslot * WU + TW] = (frow && c0 + TW < n1) ? (T(2) * xt - xe) : T(0);
+      if (fsub == 0) U[fslot * WU + TW] = (frow && c0 + TW < n1) ? reflect(xt, xe) : T(0);
     }
 #else
     static_assert(PCS_NM_COOP65 || !PCS_NM_COLS, "the column layout computes the 65th column cooperatively");
@@ -878,17 +862,10 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
       const bool own = lr >= s0 && lr < s1 && gr < n0 && ccin;
       const T d0 = r_last ? T(0) : (uc[o + 1] - uc[o]);
       const T d1 = cclast ? T(0) : (uright - uc[o]);
-      const T w0v = zv0 + P.sigma * (d0 * P.inv_step0), w1v = zv1 + P.sigma * (d1 * P.inv_step1);
-      T zt0, zt1;
-      if (HK == PCS_H_L21) {  // as p6f
-        const T sc = fminf(T(1), P.lam * fast_rsqrt(w0v * w0v + w1v * w1v));
-        zt0 = w0v * sc;
-        zt1 = w1v * sc;
-      } else {
-        zt0 = fminf(fmaxf(w0v, -P.lam), P.lam);
-        zt1 = fminf(fmaxf(w1v, -P.lam), P.lam);
-      }
-      const T o0 = P.rho * zt0 + P.omr * zv0, o1 = P.rho * zt1 + P.omr * zv1;
+      const T w[2] = {dual_arg(zv0, d0 * P.inv_step0, P), dual_arg(zv1, d1 * P.inv_step1, P)};
+      T zt[2];
+      fenchel_w<2, Fenchel::Direct, false>(HK, w, P, zt);
+      const T o0 = relax<false>(zt[0], zv0, P), o1 = relax<false>(zt[1], zv1, P);
       const uint32_t off = (own ? (uint32_t)(lr + s.hz) * pitch : kOOB) + co_cc;
       bstore1<PCS_NM_SAUX>(rzn0, off, o0);
       bstore1<PCS_NM_SAUX>(rzn1, off, o1);

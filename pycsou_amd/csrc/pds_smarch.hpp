@@ -284,23 +284,20 @@ __device__ __forceinline__ void smarch_task(const T* __restrict__ x, T* __restri
       if constexpr (FK == PCS_F_DENOISE) gf = xv - (m < 4 ? gr[PB].v[m] : ge[PB]);  // (2 (x + (-y))) 0.5, exact
       else if constexpr (FK == PCS_F_GRADBUF) gf = m < 4 ? gr[PB].v[m] : ge[PB];
       else if constexpr (FK == SM_F_NB) gf = (m < 4 ? gr[PB].v[m] : ge[PB]) - (m < 4 ? br[PB].v[m] : be[PB]);
-      const T xt = prox_g((xv - P.tau * gf) - P.tau * kt, gk, P.seg_a, P.seg_b);
+      const T xt = primal_prox(grad_step(xv, gf, P), kt, gk, P);
       const bool in = rrow && (m < 4 ? cin : ce_in);
-      const T u = in ? (T(2) * xt - xv) : T(0);
+      const T u = in ? reflect(xt, xv) : T(0);
       if (m < 4) {
         uo.v[m] = u;
-        const T xnew = pcs_fma(P.rho, xt, P.omr * xv);
+        const T xnew = relax<true>(xt, xv, P);
         xo.v[m] = xnew;
         const T dx = xv - xnew;
         sdx += dx * dx;
         sx += xv * xv;
         if constexpr (FK == SM_F_MASK) {  // the masked block's z_m', pointwise (K u = M u here)
           const T yv = gr[PB].v[m], zmv = mr[PB].v[m];
-          const T w = zmv + P.sigma * u;
-          const T a = w * P.inv_sigma + (-yv);  // ProxFuncPreComp: v + (-y)
-          const T pl = a - P.inv_sigma * clip1(a * P.sigma);  // prox_l1(a, 1 / sigma)
-          const T zt = w - P.sigma * (pl - (-yv));
-          const T zo = (yv == yv) ? pcs_fma(P.rho, zt, P.omr * zmv) : T(0);  // NaN y: not sampled
+          const T zt = fenchel_l1_shifted(zmv, u, yv, P);
+          const T zo = (yv == yv) ? relax<true>(zt, zmv, P) : T(0);  // NaN y: not sampled
           mo.v[m] = zo;
           const T dm = zmv - zo;
           sdm += dm * dm;
@@ -362,24 +359,11 @@ __device__ __forceinline__ void smarch_task(const T* __restrict__ x, T* __restri
         ku[0] = sw_d1_fwd<KK, RI>(w0, gr_, n0, P.inv_step0, edge);
         ku[D - 1] = sw_d1_fwd<KK, CI>(w1, i1, n1, P.inv_step1, edge);
       }
-      T w[D], v[D], zt[D];
+      T zt[D];
+      fenchel<D, Fenchel::Literal, true>(HK, zv, m, ku, P, zt);
 #pragma unroll
       for (int d = 0; d < D; ++d) {
-        w[d] = zv[d].v[m] + P.sigma * ku[d];
-        v[d] = w[d] * P.inv_sigma;
-      }
-      if constexpr (D == 2 && HK == PCS_H_L21) {  // w - sigma * (max(1 - t/||v||, 0) v), penalty.py:551-557
-        T f = T(1) - P.t_h * fast_rsqrt(pcs_fma(v[0], v[0], v[D - 1] * v[D - 1]));
-        f = f > T(0) ? f : T(0);
-#pragma unroll
-        for (int d = 0; d < D; ++d) zt[d] = w[d] - P.sigma * (f * v[d]);
-      } else {  // w - sigma * (v - t*clip(v/t)), func/base.py:239-240
-#pragma unroll
-        for (int d = 0; d < D; ++d) zt[d] = w[d] - P.sigma * (v[d] - P.t_h * clip1(v[d] * P.inv_t_h));
-      }
-#pragma unroll
-      for (int d = 0; d < D; ++d) {
-        o[d].v[m] = pcs_fma(P.rho, zt[d], P.omr * zv[d].v[m]);
+        o[d].v[m] = relax<true>(zt[d], zv[d].v[m], P);
         const T ed = zv[d].v[m] - o[d].v[m];
         sdz += ed * ed;
         sz += zv[d].v[m] * zv[d].v[m];

@@ -26,6 +26,7 @@
 
 #include "common.hpp"
 #include "pds_ctrl.hpp"
+#include "pds_update.hpp"
 
 // Diagnostics only: bit k skips phase k (0 P1, 1 P2, 2 P3, 3 P4, 4 P5, 5 P6, 6 X->LDS,
 // 7 z->LDS) so rocprof counters can be attributed to phases.  Results are wrong.
@@ -42,11 +43,6 @@ struct RU4 {
 };
 constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
-
-template <typename T>
-struct G4 {
-  T v[4];
-};
 
 template <typename T>
 __device__ __forceinline__ G4<T> ld4(const T* p);
@@ -173,35 +169,6 @@ __device__ __forceinline__ void col_item(const T* __restrict__ in, int pin, int 
       }
     }
   }
-}
-
-template <typename T>
-struct Params {
-  T tau, sigma, inv_sigma, rho, omr, t_h, inv_t_h, inv_step0, inv_step1, seg_a, seg_b;
-  T lam;  // H = lam * L1 / L21 (the normal-operator kernel's fenchel step: clip / scale by lam)
-  int unit0, unit1;  // step == 1: skip the scaling (exact)
-};
-
-template <typename T>
-__device__ __forceinline__ T prox_g(T v, int gk, T a, T b) {
-  if (gk == PCS_G_NONNEG) return (v < T(0)) ? T(0) : v;  // math/prox.py:295-297
-  if (gk == PCS_G_SEGMENT) {                             // math/prox.py:340-343
-    v = (v < a) ? a : v;
-    return (v > b) ? b : v;
-  }
-  return v;
-}
-
-__device__ __forceinline__ float fast_rsqrt(float v) { return __builtin_amdgcn_rsqf(v); }
-// fp64: v_rsq_f64 and two Newton steps (each squares the relative error: ~1 ulp) instead of 1.0 / sqrt(v),
-// an IEEE square root and an IEEE division (~25 fp64 instructions on the fenchel prox's path).  v = 0 and
-// v = +inf keep the hardware's exact +inf / 0 (a Newton step would turn them into NaN)
-__device__ __forceinline__ double fast_rsqrt(double v) {
-  const double y0 = __builtin_amdgcn_rsq(v);
-  const double h = 0.5 * v;
-  double y = y0 * __builtin_fma(-h * y0, y0, 1.5);
-  y = y * __builtin_fma(-h * y, y, 1.5);
-  return (v == 0.0 || v == __builtin_huge_val()) ? y0 : y;
 }
 
 template <typename T>
@@ -382,11 +349,12 @@ __device__ __forceinline__ void pds2d_tile(const T* __restrict__ x, T* __restric
       if (INT || c < n1 - 1) d1 -= z1b.v[m];
       const T a0 = P.unit0 ? d0 : d0 * P.inv_step0;
       const T a1 = P.unit1 ? d1 : d1 * P.inv_step1;
-      const T xt = prox_g((xv - P.tau * gf) - P.tau * (a0 + a1), gk, P.seg_a, P.seg_b);
+      const T xt = primal_prox(grad_step(xv, gf, P), a0 + a1, gk, P);
       bool in = true;
       if (!INT) in = (gr >= 0 && gr < n0 && c < n1 && lr <= s.rows);
-      uo.v[m] = in ? (T(2) * xt - xv) : T(0);
-      const T xnew = P.rho * xt + P.omr * xv;
+      const T ur = reflect(xt, xv);
+      uo.v[m] = in ? ur : T(0);
+      const T xnew = relax<false>(xt, xv, P);
       xo.v[m] = xnew;
       bool own = (i < TH) && (4 * g + m < TW);
       if (!INT) own = own && in && lr < s.rows;
@@ -438,20 +406,19 @@ __device__ __forceinline__ void pds2d_tile(const T* __restrict__ x, T* __restric
       T d1 = (INT || c < n1 - 1) ? (uright - uc.v[m]) : T(0);
       const T ku0 = P.unit0 ? d0 : d0 * P.inv_step0;
       const T ku1 = P.unit1 ? d1 : d1 * P.inv_step1;
-      const T w0v = zv0.v[m] + P.sigma * ku0, w1v = zv1.v[m] + P.sigma * ku1;
-      const T v0 = w0v * P.inv_sigma, v1 = w1v * P.inv_sigma;
+      const T w0v = dual_arg(zv0.v[m], ku0, P), w1v = dual_arg(zv1.v[m], ku1, P);
+      const T v0 = dual_scaled(w0v, P), v1 = dual_scaled(w1v, P);
       T zt0, zt1;
-      if (hk == PCS_H_L21) {  // w - sigma * (max(1 - t/||v||, 0) v), penalty.py:551-557
-        T f = T(1) - P.t_h * fast_rsqrt(v0 * v0 + v1 * v1);
-        f = f > T(0) ? f : T(0);
-        zt0 = w0v - P.sigma * (f * v0);
-        zt1 = w1v - P.sigma * (f * v1);
-      } else {  // w - sigma * (v - t*clip(v/t)), func/base.py:239-240
-        zt0 = w0v - P.sigma * (v0 - P.t_h * clip1(v0 * P.inv_t_h));
-        zt1 = w1v - P.sigma * (v1 - P.t_h * clip1(v1 * P.inv_t_h));
+      if (hk == PCS_H_L21) {
+        const T f = l21_shrink(norm2<false>(v0, v1), P);
+        zt0 = fenchel_l21(w0v, v0, f, P);
+        zt1 = fenchel_l21(w1v, v1, f, P);
+      } else {
+        zt0 = fenchel_l1(w0v, v0, P);
+        zt1 = fenchel_l1(w1v, v1, P);
       }
-      o0.v[m] = P.rho * zt0 + P.omr * zv0.v[m];
-      o1.v[m] = P.rho * zt1 + P.omr * zv1.v[m];
+      o0.v[m] = relax<false>(zt0, zv0.v[m], P);
+      o1.v[m] = relax<false>(zt1, zv1.v[m], P);
       if (cin) {
         const double e0 = (double)zv0.v[m] - (double)o0.v[m], e1 = (double)zv1.v[m] - (double)o1.v[m];
         part[2] += e0 * e0 + e1 * e1;

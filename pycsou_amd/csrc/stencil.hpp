@@ -95,11 +95,9 @@ __device__ __forceinline__ T d2_adj_core(const T* __restrict__ y, I p, I s, I i,
 // row- and plane-marching steps: pds_smarch.hpp, pds3d.hip);
 // INT: the sample is known to lie >= 2 samples inside the axis (no edge rule applies).  hipcc
 // contracts a * b + c freely (-ffp-contract=fast ignores the fp pragmas), so every formula here is
-// written with no mul feeding an add -- (difference) * step, or an explicit fma -- and the interior
-// and the edge instantiations of a sample give the same bits: a pixel's result does not depend on
-// which row step or slab it falls in (slabs are bitwise equal to the whole image)
-__device__ __forceinline__ float pcs_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double pcs_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+// written with no mul feeding an add -- (difference) * step, or an explicit fma (pcs_fma, common.hpp)
+// -- and the interior and the edge instantiations of a sample give the same bits: a pixel's result
+// does not depend on which row step or slab it falls in (slabs are bitwise equal to the whole image)
 
 template <int KIND, bool INT, typename T>
 __device__ __forceinline__ T sw_d1_fwd(const T (&w)[5], int i, int n, T ih, int edge) {

@@ -440,3 +440,17 @@ def test_l21_label_groups_csr():
     for g in range(uniq.size):
         members = order[off[g]:off[g + 1]]
         np.testing.assert_array_equal(members, np.flatnonzero(inv == g))  # ascending element order
+
+
+def test_update_rule_stated_once():
+    """The per-element PDS update rule (prox_G, the Fenchel prox's clip and group norm) is written in
+    csrc/pds_update.hpp alone: the fused step kernels call its helpers, and none spells it out again."""
+    csrc = os.path.join(REPO, 'pycsou_amd', 'csrc')
+    sources = sorted(f for f in os.listdir(csrc) if f.startswith('pds') and f != 'pds_update.hpp')
+    assert 'pds3d.hip' in sources and 'pds_nmarch.hpp' in sources and len(sources) >= 14, sources
+    names = re.compile(r'\b(fast_rsqrt|clip1|prox_g)\(')
+    found = [(f, i + 1, m.group(1)) for f in sources
+             for i, line in enumerate(open(os.path.join(csrc, f))) for m in names.finditer(line)]
+    assert not found, found
+    body = open(os.path.join(csrc, 'pds_update.hpp')).read()
+    assert {'fast_rsqrt', 'clip1', 'prox_g'} <= set(names.findall(body))

@@ -1,4 +1,4 @@
-// Round 5: accuracy of the fp64 fast_rsqrt (pds_tile.hpp: v_rsq_f64 + two Newton steps) against 1 / sqrt in
+// Round 5: accuracy of the fp64 fast_rsqrt (pds_update.hpp: v_rsq_f64 + two Newton steps) against 1 / sqrt in
 // long double on the host, over 2^20 values spread across [1e-300, 1e300] plus 0 and +inf.  Prints the largest
 // relative error (in ulps of the correctly rounded result).  Build: hipcc --offload-arch=gfx950 -O3
 #include <hip/hip_runtime.h>
@@ -7,7 +7,7 @@
 #include <cstdlib>
 #include <vector>
 #include "../pycsou_amd/csrc/common.hpp"
-#include "../pycsou_amd/csrc/pds_tile.hpp"
+#include "../pycsou_amd/csrc/pds_update.hpp"
 __global__ void k(const double* v, double* o, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) o[i] = pcs::fast_rsqrt(v[i]);
