@@ -67,6 +67,29 @@ __device__ __forceinline__ int row_lane_group(int l5) {
 // global data another wave of the launch wrote.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// ---------------------------------------------------------------- workgroup -> task maps
+// Workgroups b, b + 8, ... of a launch run on one XCD (MI355X_MICROARCH.md).  Both maps give an XCD a
+// contiguous share of the task list, so the workgroups that share an L2 work on neighbouring tasks.
+//
+// One workgroup per task (a bijection on [0, ntasks)): XCD x takes q or q + 1 consecutive tasks
+// (q = ntasks / 8, the first ntasks % 8 XCDs one more), its k-th workgroup the k-th of them.
+__device__ __forceinline__ int xcd_task(int b, int ntasks) {
+  const int q = ntasks / 8, r = ntasks % 8, xcd = b % 8, k = b / 8;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+}
+// Persistent workgroups (gridDim.x of them, any number): XCD x (nbx workgroups) owns the share of the task list
+// proportional to nbx; its k-th workgroup takes tasks t0, t0 + stride, ... below end.
+struct XcdShare {
+  int64_t t0, end, stride;
+};
+__device__ __forceinline__ XcdShare xcd_share(int64_t ntasks) {
+  const int64_t b = blockIdx.x, nb = gridDim.x, xcd = b % 8, k = b / 8, q = nb / 8, r = nb % 8;
+  const int64_t nbx = q + (xcd < r ? 1 : 0);
+  const int64_t before = xcd * q + (xcd < r ? xcd : r);  // workgroups of the XCDs below x
+  const int64_t lo = ntasks * before / nb, hi = ntasks * (before + nbx) / nb;
+  return {lo + k, hi, nbx};
+}
+
 // Buffer descriptors (hardware range check): a byte offset at or past the descriptor's size
 // reads 0 / drops the store.  Offsets are built from parts that are either valid or kOOB; with
 // every view <= 2^30 bytes a sum with any kOOB part is >= the size and two kOOB parts cannot wrap.

@@ -618,19 +618,8 @@ __global__ __launch_bounds__(256) void k_sep2d_march(const T* __restrict__ in, T
     ha[t] = t < ka ? ha_[t] : T(0);
     hb[t] = t < kb ? hb_[t] : T(0);
   }
-  // XCD-aware task map: XCD x (blocks b % 8 == x, nbx of them) owns a contiguous share of the
-  // task list proportional to nbx; its k-th block takes lo + k, lo + k + nbx, ... so that the
-  // blocks running together on one XCD work on consecutive tasks
-  int64_t t0, t_end, t_stride;
-  {
-    const int64_t b = blockIdx.x, nb = gridDim.x, xcd = b % 8, k = b / 8, q = nb / 8, r = nb % 8;
-    const int64_t nbx = q + (xcd < r ? 1 : 0);
-    const int64_t before = xcd * q + (xcd < r ? xcd : r);  // blocks of the XCDs below x
-    const int64_t lo = ntasks * before / nb, hi = ntasks * (before + nbx) / nb;
-    t0 = lo + k;
-    t_end = hi;
-    t_stride = nbx;
-  }
+  const XcdShare own = xcd_share(ntasks);  // XCD x owns a contiguous share of the task list (common.hpp)
+  const int64_t t0 = own.t0, t_end = own.end, t_stride = own.stride;
   if (t0 >= t_end) return;
   const int tid = threadIdx.x, g = tid & 31, hrow = tid >> 5;
   auto task_at = [&](int64_t t) {  // the first step of task t

@@ -33,24 +33,13 @@
 
 #include "common.hpp"
 
-// diagnostics variants (PCS_LIB_PATH builds, tools/conv2d_bench.py): register prefetch of the
-// next block's rows (PRE).  Measured on 4096^2 fp32 (r2 session): SGPR taps (scalar loads),
-// single-buffered input rows, 3-4 waves/SIMD register budgets and a one-burst read schedule
-// were all equal or slower than this configuration (96.5-116 us against 97-98 us for k = 15).
-#ifndef PCS_CORR_PRE
-#define PCS_CORR_PRE 1
-#endif
-// spread the next row's LDS reads through the current row's FMAs (sched_group_barrier)
-// instead of issuing them as one burst ahead of the FMAs
-#ifndef PCS_CORR_SPREAD
-#define PCS_CORR_SPREAD 1
-#endif
+// The next block's rows are prefetched into registers and the next row's LDS reads are spread through the
+// current row's FMAs.  Measured on 4096^2 fp32: SGPR taps (scalar loads), single-buffered input rows (no
+// prefetch), 3-4 waves/SIMD register budgets and a one-burst read schedule were all equal or slower
+// (96.5-116 us against 97-98 us for k = 15).
+// the spread covers the first 1 / PCS_CORR_SPREAD_DIV of a row's FMAs
 #ifndef PCS_CORR_SPREAD_DIV
 #define PCS_CORR_SPREAD_DIV 2
-#endif
-// ablations (timing only, wrong results): 1 = no FMAs, 2 = no ring fill
-#ifndef PCS_CORR_ABLATE
-#define PCS_CORR_ABLATE 0
 #endif
 
 namespace pcs {
@@ -144,11 +133,7 @@ __global__ __launch_bounds__(256) void k_corr2d(const T* __restrict__ x, T* __re
   T* ring = reinterpret_cast<T*>(smem_raw);
   T* tl = reinterpret_cast<T*>(smem_raw + Cf::RING_BYTES);  // taps [K][KP], correlation order
 
-  int task = blockIdx.x;
-  {  // XCD-aware bijective remap: blocks b, b+8, ... share an XCD -> adjacent strips of a segment
-    const int bb = blockIdx.x, qq = ntasks / 8, rr = ntasks % 8, xcd = bb % 8, kk = bb / 8;
-    task = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + kk;
-  }
+  const int task = xcd_task((int)blockIdx.x, ntasks);  // XCD-aware (common.hpp)
   const int strip = task % nstrips;
   const int64_t sg = task / nstrips;
   const int64_t r0 = sg * seg;
@@ -188,10 +173,9 @@ __global__ __launch_bounds__(256) void k_corr2d(const T* __restrict__ x, T* __re
       }
     }
   };
-  if (PCS_CORR_PRE && PCS_CORR_ABLATE != 2) issue(0);
+  issue(0);
 
   for (int blk = 0; blk < nblk; ++blk) {
-    if (!PCS_CORR_PRE && PCS_CORR_ABLATE != 2) issue(blk);
     {  // land the prefetched rows: window rows blk*TH + K-1 + rr -> ring slot mod RS
       const int s0 = (int)(((int64_t)blk * TH + (K - 1)) % RS);
 #pragma unroll
@@ -206,7 +190,7 @@ __global__ __launch_bounds__(256) void k_corr2d(const T* __restrict__ x, T* __re
       }
     }
     lds_barrier();
-    if (PCS_CORR_PRE && PCS_CORR_ABLATE != 2 && blk + 1 < nblk) issue(blk + 1);
+    if (blk + 1 < nblk) issue(blk + 1);
 
     const int64_t g = r0 + (int64_t)blk * TH + trow;  // this thread's output row
     // a wave whose 16 rows all lie past the segment skips the arithmetic
@@ -250,10 +234,6 @@ __global__ __launch_bounds__(256) void k_corr2d(const T* __restrict__ x, T* __re
         }
       };
       auto fmas = [&](const T (&in)[WIN], const T (&h)[KP]) {
-        if (PCS_CORR_ABLATE == 1) {
-          acc[0] += in[LEFT] * h[0];
-          return;
-        }
 #pragma unroll
         for (int j = 0; j < K; ++j)
 #pragma unroll
@@ -280,12 +260,10 @@ __global__ __launch_bounds__(256) void k_corr2d(const T* __restrict__ x, T* __re
       auto spread = [&]() {
         constexpr int NR = NB + KP / V;
         constexpr int GV = C * K / (PCS_CORR_SPREAD_DIV * NR);
-        if (PCS_CORR_SPREAD) {
 #pragma unroll
-          for (int t = 0; t < NR; ++t) {
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
-            __builtin_amdgcn_sched_group_barrier(0x002, GV, 0);  // VALU
-          }
+        for (int t = 0; t < NR; ++t) {
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
+          __builtin_amdgcn_sched_group_barrier(0x002, GV, 0);  // VALU
         }
         __builtin_amdgcn_sched_barrier(0);
       };
@@ -304,7 +282,6 @@ __global__ __launch_bounds__(256) void k_corr2d(const T* __restrict__ x, T* __re
         if (++s == RS) s = 0;
         rd(ib, s);
         rdt(hb, q + 1);
-        if (!PCS_CORR_SPREAD) __builtin_amdgcn_sched_barrier(0);
         fmas(ia, ha);
         spread();
         keep(ib);
@@ -312,7 +289,6 @@ __global__ __launch_bounds__(256) void k_corr2d(const T* __restrict__ x, T* __re
         if (++s == RS) s = 0;
         rd(ia, s);
         rdt(ha, q + 2);
-        if (!PCS_CORR_SPREAD) __builtin_amdgcn_sched_barrier(0);
         fmas(ib, hb);
         spread();
         keep(ia);

@@ -469,15 +469,6 @@ int pcs_pds2d_run(const pcs_pds2d_args* a, int64_t n, hipStream_t st) {
 
 int64_t pcs_ctrl_bytes(void) { return 64; }
 
-#ifdef PCS_STAMPS
-// diagnostic build only: copy the march kernel's per-segment stamp totals to the host
-int pcs_debug_stamps(void* host, int64_t bytes) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_pcs_stamps), (size_t)bytes, 0, hipMemcpyDeviceToHost) == hipSuccess
-             ? 0
-             : PCS_ELAUNCH;
-}
-#endif
-
 int pcs_ctrl_init2(void* ctrl, int min_iter, int max_iter, double thr, int has_dual, int hist_len, hipStream_t st) {
   if (!ctrl || hist_len < 2) return PCS_EINVAL;
   k_ctrl_init<<<1, 1, 0, st>>>((Ctrl*)ctrl, min_iter, max_iter, thr, has_dual, hist_len);

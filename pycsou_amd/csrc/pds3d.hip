@@ -22,10 +22,6 @@
 #include "pds_march.hpp"
 #include "stencil.hpp"
 
-#ifndef PCS_3D_PRIO  // wave priority 3 while the next plane's loads issue; diagnostics
-#define PCS_3D_PRIO 0
-#endif
-
 
 namespace pcs {
 
@@ -228,11 +224,7 @@ __global__ __launch_bounds__(FK == PCS_F_CONV0 ? 2 * K3<T>::NT : K3<T>::NT, FK =
   __shared__ int flag[2];
   if (ctrl != nullptr && ctrl->stopped != 0) return;  // loop already stopped (solver.py:65-66)
 
-  int task;
-  {  // XCD-aware bijective remap: consecutive tasks (neighbouring tiles of a segment) share an XCD
-    const int b = blockIdx.x, q = ntasks / 8, r = ntasks % 8, xcd = b % 8, k = b / 8;
-    task = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int task = xcd_task((int)blockIdx.x, ntasks);  // XCD-aware (common.hpp)
   const int per_plane = tiles1 * tiles2;
   const int seg = task / per_plane, t12 = task - seg * per_plane;
   const int ty = t12 / tiles2, tx = t12 - ty * tiles2;
@@ -418,13 +410,7 @@ __global__ __launch_bounds__(FK == PCS_F_CONV0 ? 2 * K3<T>::NT : K3<T>::NT, FK =
     G4<T> gv4;
     if constexpr (FK != PCS_F_NULL && !FOLD) gv4 = gr;
     land(slot);
-#if PCS_3D_PRIO
-    __builtin_amdgcn_s_setprio(3);
-#endif
     if (p < p_end) prefetch(p + 1);
-#if PCS_3D_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
     lds_barrier();
     const int fl = launder(flags);
     // ---- U items: x_t, u on rows [r1, r1 + T1], cols [c2, c2 + WG) of plane p; x' on own cells
@@ -597,9 +583,6 @@ constexpr int k3g_sets() { return sizeof(T) == 4 ? PCS_3DG_SETS32 : PCS_3DG_SETS
 template <typename T>
 constexpr int k3g_rows() { return sizeof(T) == 4 ? PCS_3DG_ROWS32 : PCS_3DG_ROWS64; }
 
-#ifndef PCS_3DG_ROWFORM  // column-border tiles with the row axis interior get their own code form (A/B knob)
-#define PCS_3DG_ROWFORM 1
-#endif
 #ifndef PCS_3DG_MINB  // workgroups per CU the register budget targets (diagnostics builds override)
 #define PCS_3DG_MINB 1
 #endif
@@ -623,11 +606,7 @@ __global__ __launch_bounds__(k3g_nt<T>(), PCS_3DG_MINB) void k_pds3d_gen(const T
   __shared__ int flag[2];
   if (ctrl != nullptr && ctrl->stopped != 0) return;  // loop already stopped (solver.py:65-66)
 
-  int task;
-  {  // XCD-aware bijective remap: consecutive tasks (neighbouring tiles of a segment) share an XCD
-    const int b = blockIdx.x, q = ntasks / 8, r = ntasks % 8, xcd = b % 8, k = b / 8;
-    task = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int task = xcd_task((int)blockIdx.x, ntasks);  // XCD-aware (common.hpp)
   const int per_plane = tiles1 * tiles2;
   const int seg = task / per_plane, t12 = task - seg * per_plane;
   const int ty = t12 / tiles2, tx = t12 - ty * tiles2;
@@ -666,7 +645,7 @@ __global__ __launch_bounds__(k3g_nt<T>(), PCS_3DG_MINB) void k_pds3d_gen(const T
   const bool row_int = r1 - 1 >= 2 && r1 + T1 <= v.n1 - 3, col_int = c2 - 4 >= 2 && c2 + TW + 3 <= v.n2 - 3;
   const bool tile_int = row_int && col_int;
   // a tile on a column border only (most border tiles: every plane row has two) keeps the row axis interior
-  const bool row_only = PCS_3DG_ROWFORM && row_int && !col_int;
+  const bool row_only = row_int && !col_int;
 
   // loads run two planes ahead: iteration p lands set p & 1 and refills it with plane p + 2's data
   // (C4 centred: 1.41 ms with one set; the wait for the next plane's loads was exposed at two waves

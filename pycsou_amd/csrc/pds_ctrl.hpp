@@ -92,12 +92,9 @@ struct RedOut {
 // and every workgroup still arrives at the reduction counters (with zero partials), which
 // then stay consistent for the next run of the plan.
 // Single-GPU launches (no sums output) read the stop flag at entry but consume it inside the task, after
-// the task's first loads have issued (PCS_DEFER_STOP): the flag's latency overlaps theirs instead of
-// preceding them.  The task returns before its first store when the flag is set.
-#ifndef PCS_DEFER_STOP
-#define PCS_DEFER_STOP 1
-#endif
-__device__ __forceinline__ bool stop_deferred(const RedOut& ro) { return PCS_DEFER_STOP && ro.sums == nullptr; }
+// the task's first loads have issued: the flag's latency overlaps theirs instead of preceding them.  The task
+// returns before its first store when the flag is set.
+__device__ __forceinline__ bool stop_deferred(const RedOut& ro) { return ro.sums == nullptr; }
 __device__ __forceinline__ int stop_flag_early(const Ctrl* ctrl, const RedOut& ro) {
   return stop_deferred(ro) && ctrl != nullptr ? ctrl->stopped : 0;
 }
@@ -158,14 +155,9 @@ __device__ __forceinline__ bool fin_slot(const RedOut& ro, int64_t nblocks, Ctrl
 // Called by every thread of every workgroup after thread 0's `part` holds the block sums.
 // `flag` is a 2-int LDS scratch.  With ro.sums the last group writes the sums instead of
 // running finalize_from.
-// ablation (timing only, the loop control never advances; PCS_LIB_PATH builds): 1 = no reduction at all
-#ifndef PCS_RED_ABL
-#define PCS_RED_ABL 0
-#endif
 __device__ __forceinline__ void reduce_and_finalize(const double (&part)[4], double* __restrict__ partials,
                                                     int64_t nblocks, void* ws, Ctrl* ctrl, double* hist, int* flag,
                                                     RedOut ro = RedOut{nullptr, nullptr, 0, nullptr}) {
-  if (PCS_RED_ABL & 1) return;
   const int tid = threadIdx.x;
   const int64_t b = blockIdx.x;
   const int64_t ngr = red_groups(nblocks);

@@ -26,17 +26,9 @@ namespace pcs {
 
 enum { KK_LAP = 3 };  // KK: PCS_FORWARD / PCS_BACKWARD / PCS_CENTERED gradients, or the Laplacian
 
-// phase barriers: LDS-only (s_waitcnt lgkmcnt(0) + s_barrier) by default -- no wave reads global
-// data another wave of the launch wrote, so the x' stores of the U phase need not have landed
-// before the Z phase (__syncthreads' release fence would wait for them); PCS_GEN_LDSBAR=0 restores it
-#ifndef PCS_GEN_LDSBAR
-#define PCS_GEN_LDSBAR 1
-#endif
-#if PCS_GEN_LDSBAR
-#define PCS_GEN_BARRIER() lds_barrier()
-#else
-#define PCS_GEN_BARRIER() __syncthreads()
-#endif
+// phase barriers are lds_barrier(): LDS-only (s_waitcnt lgkmcnt(0) + s_barrier) -- no wave reads global data
+// another wave of the launch wrote, so the x' stores of the U phase need not have landed before the Z phase
+// (__syncthreads' release fence would wait for them)
 #ifndef PCS_GEN_TR
 #define PCS_GEN_TR 32
 #endif
@@ -188,7 +180,7 @@ __device__ __forceinline__ void gen_tile(const T* __restrict__ x, T* __restrict_
         if (e < G::NZI) st4(Z + d * ZS + 4 * e, zr[d][k]);  // row rr, group g at rr * CW + 4 g = 4 e
       }
   }
-  PCS_GEN_BARRIER();
+  lds_barrier();
   // ---- U items: x_t, u on rows [r0 - 2, r0 + TR + 2) x columns [c0 - 2, c0 + TC + 2); x' on the tile
 #pragma unroll
   for (int k = 0; k < G::KU; ++k) {
@@ -233,7 +225,7 @@ __device__ __forceinline__ void gen_tile(const T* __restrict__ x, T* __restrict_
       }
     }
   }
-  PCS_GEN_BARRIER();
+  lds_barrier();
   // ---- z' on the tile
 #pragma unroll
   for (int k = 0; k < G::KO; ++k) {
@@ -304,11 +296,7 @@ __global__ __launch_bounds__(GenG::NT) void k_pds2d_gen(const T* __restrict__ x,
   __shared__ double red[4 * (G::NT / 64)];
   __shared__ int flag[2];
   if (ctrl != nullptr && ctrl->stopped != 0) return;  // loop already stopped (solver.py:65-66)
-  int task;
-  {  // XCD-aware bijective remap: consecutive tiles of a row share an XCD (their halo lines)
-    const int b = blockIdx.x, q = ntasks / 8, r = ntasks % 8, xcd = b % 8, k = b / 8;
-    task = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int task = xcd_task((int)blockIdx.x, ntasks);  // XCD-aware (common.hpp)
   const int ty = task / geo.tiles1, tx = task - ty * geo.tiles1;
   const int r0 = ty * G::TR, c0 = tx * G::TC;
   double part[4] = {0.0, 0.0, 0.0, 0.0};

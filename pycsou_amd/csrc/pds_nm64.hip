@@ -383,10 +383,7 @@ __device__ __forceinline__ void nm64_task(const double* __restrict__ x, double* 
   }
   // ================= march
   const int nsteps = (s1 - s0 + TS - 1) / TS;
-#ifndef PCS_NM64_ALLINT  // diagnostics (timing only, wrong border values): every strip and step on the interior form
-#define PCS_NM64_ALLINT 0
-#endif
-  const bool cint = PCS_NM64_ALLINT || (cb >= 2 && cb + M::CW + 2 <= n1);  // the strip's columns [cb, cb + 64) >= 2 inside
+  const bool cint = cb >= 2 && cb + M::CW + 2 <= n1;  // the strip's columns [cb, cb + 64) >= 2 inside
   // one step; RI: its U rows [a + 1, a + 33) and Z rows [a, a + 32) >= 2 inside the image
   auto step = [&](int a, auto ri, auto ci) {
     lds_barrier();  // step k - 1 done with the z tiles and the u ring; this step's x rows have landed
@@ -410,17 +407,10 @@ __device__ __forceinline__ void nm64_task(const double* __restrict__ x, double* 
     __builtin_amdgcn_s_waitcnt((6 & 15) | (7 << 4) | (15 << 8));
     store_x(xnx, a + TS + 2 * H + 1, TS);
   };
-  auto rows_in = [&](int a) { return PCS_NM64_ALLINT || (s.row0 + a >= 2 && s.row0 + a + TS + 3 <= n0); };
-#ifndef PCS_NM64_PEEL  // diagnostics: 0 = one loop choosing the form per step
-#define PCS_NM64_PEEL 1
-#endif
-// the border strips' interior-row steps on a form with the row axis interior (0: the all-axes edge form)
-#ifndef PCS_NM64_ROWFORM
-#define PCS_NM64_ROWFORM 1
-#endif
+  auto rows_in = [&](int a) { return s.row0 + a >= 2 && s.row0 + a + TS + 3 <= n0; };
   using Tt = std::true_type;
   using Ff = std::false_type;
-  const bool peel = PCS_NM64_PEEL && rows_in(s0) && rows_in(s0 + (nsteps - 1) * TS);
+  const bool peel = rows_in(s0) && rows_in(s0 + (nsteps - 1) * TS);
   if (cint) {
     if (peel) {
       // every step of the task interior (uniform): a loop holding the interior form only -- with both
@@ -433,7 +423,7 @@ __device__ __forceinline__ void nm64_task(const double* __restrict__ x, double* 
         else step(a, Ff{}, Ff{});
       }
     }
-  } else if (PCS_NM64_ROWFORM && peel) {  // a border strip whose rows are all interior: the column rules only
+  } else if (peel) {  // a border strip whose rows are all interior: the row axis interior, the column rules only
     for (int k = 0; k < nsteps; ++k) step(s0 + k * TS, Tt{}, Ff{});
   } else {
     for (int k = 0; k < nsteps; ++k) step(s0 + k * TS, Ff{}, Ff{});
@@ -455,14 +445,10 @@ __global__ __launch_bounds__(512, 1) void k_pds2d_nmarch64(const double* __restr
   __shared__ double red[4 * (M::NT / 64)];
   __shared__ int flag[2];
   if (fin_slot(ro, ntasks, ctrl, hist, red, flag)) return;  // deferred finalization (pds_ctrl.hpp)
-  const int stop_raw = stop_flag_early(ctrl, ro);  // consumed in the task (PCS_DEFER_STOP)
+  const int stop_raw = stop_flag_early(ctrl, ro);  // consumed in the task
   const bool stopped = !stop_deferred(ro) && stop_requested(ctrl, ro, flag);
   if (stopped && ro.sums == nullptr) return;  // loop already stopped (solver.py:65-66)
-  int task;  // XCD-aware bijective remap: blocks b, b+8, ... share an XCD -> adjacent strips
-  {
-    const int bb = (int)blockIdx.x - fin_shift(ro), q = ntasks / 8, r = ntasks % 8, xcd = bb % 8, k = bb / 8;
-    task = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int task = xcd_task((int)blockIdx.x - fin_shift(ro), ntasks);  // XCD-aware (common.hpp)
   const int seg = task / tiles_x, strip = task - seg * tiles_x;
   int s0, s1;
   band_rows(bd, seg, s0, s1);

@@ -38,9 +38,6 @@
 #ifndef PCS_NM_PF
 #define PCS_NM_PF 2
 #endif
-#ifndef PCS_NM_EDGE
-#define PCS_NM_EDGE 1
-#endif
 // cache-policy bits of the x' / z' stores (16 = sc1: written through, not left dirty in L2)
 // C2 2048^2: 31.4 against 32.3 us per iteration, C3 4096^2: 112.7 against 113.9 us (two alternating
 // reps each, profiles/r3_store_policy_ab.txt)
@@ -75,13 +72,6 @@ __device__ __forceinline__ float lds1(const float* p) {
   return *(lds_f1)(p);
 }
 
-// wave priority 3 while a step's loads issue (s_setprio), 0 for its LDS / VALU phases: the loads
-// of every wave go out ahead of the other waves' FMAs -- 113.1-113.6 against 115.9-116.5 us
-// back to back (4 alternating reps, tools/march_ablate.py); PCS_NM_PRIO=0 drops it
-#ifndef PCS_NM_PRIO
-#define PCS_NM_PRIO 1
-#endif
-
 // s_waitcnt vmcnt(N) alone (expcnt / lgkmcnt left at their maxima)
 template <int N>
 __device__ __forceinline__ void vm_wait() {
@@ -100,26 +90,6 @@ __device__ __forceinline__ G4<float> bload4a(Rsrc r, uint32_t off) {
   return {{__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])}};
 }
 
-// step 0's x rows loaded with the prologue's own rows (1: one exposed load latency per segment instead of
-// two) or after the prologue's PV (0).  C3 106.7-106.9 against 107.0-107.8 us back to back, c3_cen
-// 135.7-136.0 against 138.0-138.1 (profiles/r3_ck43_xe_*ab.txt)
-#ifndef PCS_NM_XEARLY
-#define PCS_NM_XEARLY 1
-#endif
-
-// forward kernel: the G = 0 problem (gk == PCS_G_NULL, the C3 benchmark's) runs a copy of the task compiled
-// with that constant (1), so that prox_g's scalar branches on gk -- one per element, four per thread and
-// step -- and the live gk / seg_a / seg_b leave its loop; other G keep the general copy.  0: one copy
-#ifndef PCS_NM_GKSPLIT
-#define PCS_NM_GKSPLIT 1
-#endif
-
-// forward kernel: the strip's 65th column by 16 lanes per output (1) or by the last group's 4 lanes
-// per wave in a serial 29-read branch (0)
-#ifndef PCS_NM_COOP65
-#define PCS_NM_COOP65 1
-#endif
-
 // sum over the 16-lane DPP row holding the lane (every lane of the row gets the sum; the lanes of a
 // row add in different orders, so only one lane's value is used): row_ror 8, 4, 2, 1
 __device__ __forceinline__ float row_sum16(float v) {
@@ -130,29 +100,9 @@ __device__ __forceinline__ float row_sum16(float v) {
   return v;
 }
 
-// forward kernel: PV / update / P6 in the column layout (1: a thread owns one column of the wave's four
-// rows -- b32 LDS reads, each t row of the window read once for four outputs, taps in VGPRs) or in the
-// row layout of PH (0: four columns of one row, every output row reading its own 29-row window).
-// Measured: parity green, but 123.8-125.0 against 107.1-111.0 us back to back (4 alternating reps,
-// profiles/r3_ck35_cols_ab.txt): the b32 stores / loads (12 + 4 VMEM instructions per thread and step
-// instead of 3 + 1) and the extra update reads cost more than the PV's halved LDS cycles save -- kept off
-#ifndef PCS_NM_COLS
-#define PCS_NM_COLS 0
-#endif
-
-// 4-B store through a descriptor (kOOB offsets dropped), cache-policy bits AUX as bstore4
-template <int AUX = 0>
-__device__ __forceinline__ void bstore1(Rsrc r, uint32_t off, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, (int)off, 0, AUX);
-}
-
-// GEN: the extra columns' 8-lane reduction by DPP (quad_perm xor 1, xor 2, row_half_mirror: VALU
-// latency) or by three ds_bpermute shuffles (0: LDS latency each); the same sums bit for bit
-#ifndef PCS_NMG_DPP
-#define PCS_NMG_DPP 1
-#endif
-// sum over the 8-lane group holding the lane (lanes 8 g .. 8 g + 7); every lane gets the same value, the
-// sums of __shfl_xor by 1, 2, 4 (fp addition commutes, and after the quad steps a quad holds one value)
+// sum over the 8-lane group holding the lane (lanes 8 g .. 8 g + 7) by DPP (quad_perm xor 1, xor 2,
+// row_half_mirror: VALU latency); every lane gets the same value, the sums of __shfl_xor by 1, 2, 4 bit for bit
+// (fp addition commutes, and after the quad steps a quad holds one value)
 __device__ __forceinline__ float oct_sum8(float v) {
   v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, false));   // [1,0,3,2]
   v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, false));   // [2,3,0,1]
@@ -160,16 +110,6 @@ __device__ __forceinline__ float oct_sum8(float v) {
   return v;
 }
 
-// diagnostics builds (timing only, wrong results): 1 = GEN without its extra columns, 2 = GEN with
-// interior stencils everywhere, 4 = the forward kernel without its 65th column
-#ifndef PCS_NMG_ABL
-#define PCS_NMG_ABL 0
-#endif
-// GEN: the border strips' steps with interior rows take a form with the row axis interior (only the column
-// axis on the edge rules) -- 0: every non-interior step on the all-axes form (A/B knob)
-#ifndef PCS_NMG_ROWFORM
-#define PCS_NMG_ROWFORM 1
-#endif
 // GEN: backward / centred K (KK != PCS_FORWARD) -- K^T z reads z rows lr - 1 .. lr + 1 and columns
 // c - 1 .. c + 1, K u reads u rows r - 1 .. r + 1 and columns c - 1 .. c + 1: z tiles of 18 rows (the
 // z0 tile from column c0 - 4 too), an 18-row u ring, and a sixth u / t / g column c0 - 1 (group 0,
@@ -182,8 +122,7 @@ struct NMarch {
   static constexpr int WX = TW + 2 * XL + 4;                       // x ring pitch (odd slot count)
   // t ring: 48 rows (a step's window + new rows: 4H + 2 TS <= 48 + TS) + a mirror of its first 4H
   // (rows 48..48+4H-1 repeat rows 0..4H-1), so any (4H+1)-row window starting in the ring is contiguous
-  // (forward, PCS_NM_COLS: 4H + 3, so the 4H + 4 rows of a wave's four-row window are contiguous too)
-  static constexpr int XRING = 32, TRING = 48, TMIR = (GEN || !PCS_NM_COLS) ? 4 * H : 4 * H + 3;
+  static constexpr int XRING = 32, TRING = 48, TMIR = 4 * H;
   static constexpr int WT = TW + 4, WU = TW + 4;  // t / u rows: 65 columns used (272 B; GEN: 66)
   static constexpr int SLM1 = TW + 1;             // GEN: slot of column c0 - 1 in a t / u row
   // z tiles (own __shared__ arrays, filled by LDS-DMA, lane-linear): z0 rows of 17 groups (from
@@ -256,11 +195,8 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
   const bool eright = eo >= 4;
   const int ecol = eright ? c0 + TW : c0 - 1, ets = eright ? TW : SLM1, eti = eright ? TW + 4 : 3;
   const uint32_t co_bx = GEN ? col_off(ecol, n1) : kOOB;
-  // forward, PCS_NM_COOP65: lane l of wave wv works on the 65th column of row 4 wv + l / 16, window taps
-  // l % 16 + 16 j
+  // forward: lane l of wave wv works on the 65th column of row 4 wv + l / 16, window taps l % 16 + 16 j
   const int fur = 4 * wv + (elane >> 4), fsub = elane & 15;
-  (void)fur;
-  (void)fsub;
   uint32_t co_xn[KXN];
   int rr_xn[KXN];
 #pragma unroll
@@ -323,7 +259,7 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
 #pragma unroll
     for (int m = 0; m < 4; ++m) o.v[m] = T(0);
     // taps 4 at a time (broadcast LDS reads), the next 4 read while the current ones are used
-    constexpr int NQ4 = (PCS_ABL & 2048) ? 1 : (NQ + 3) / 4;
+    constexpr int NQ4 = (NQ + 3) / 4;
     G4<T> wc = lds4(Wq + 32), wn;
 #pragma unroll
     for (int q4 = 0; q4 < NQ4; ++q4) {
@@ -345,7 +281,7 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
       pcs_fence();
       wc = wn;
     }
-    if (PCS_NM_EDGE && c0 < H) {  // exact rows of N_h on the H columns nearest the left image edge
+    if (c0 < H) {  // exact rows of N_h on the H columns nearest the left image edge
       const G4<T> x0 = lds4(xrow + XL), x1 = lds4(xrow + XL + 4);  // image columns 0..7
       const T xe[8] = {x0.v[0], x0.v[1], x0.v[2], x0.v[3], x1.v[0], x1.v[1], x1.v[2], x1.v[3]};
       const bool on = ug < 2;
@@ -357,7 +293,7 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
         for (int m = 0; m < 4; ++m) o.v[m] -= (on ? e4.v[m] : T(0)) * xe[k];
       }
     }
-    if (PCS_NM_EDGE && c0 + TW + 1 > n1 - H) {  // ... and the right one (image columns n1 - 8 .. n1 - 1)
+    if (c0 + TW + 1 > n1 - H) {  // ... and the right one (image columns n1 - 8 .. n1 - 1)
       const T* xr8 = xrow + (n1 - 8 - xc0);
       const G4<T> x0 = lds4(xr8), x1 = lds4(xr8 + 4);
       const T xf[8] = {x0.v[0], x0.v[1], x0.v[2], x0.v[3], x1.v[0], x1.v[1], x1.v[2], x1.v[3]};
@@ -388,8 +324,9 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
       }
     }
   };
-  // ---- PV + update: row lr = a + 1 + ui, columns [c, c + 4); the last group also column c + 4
-  // (the strip's 65th), in a branch of its own lanes (4 per wave: conflict-free b32 reads)
+  // ---- PV + update: row lr = a + 1 + ui, columns [c, c + 4), in the row layout of PH; then the strip's 65th
+  // column.  (A column layout of PV / update / P6 -- a thread owning one column of the wave's four rows -- lost:
+  // 123.8-125.0 against 107.1-111.0 us, profiles/r3_ck35_cols_ab.txt)
   auto pv = [&](int a, const G4<T>& bv, T b5, T bm1, int ub) {
     const int lr = a + 1 + ui, gr = s.row0 + lr;
     // GEN: the step's update rows [a+1, a+16] and z' rows [a, a+16) >= 2 samples inside the image
@@ -403,7 +340,7 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
 #pragma unroll
     for (int m = 0; m < 4; ++m) g.v[m] = T(0);
     const T* p0 = TR + M::tslot(lr - 2 * H) * WT + 4 * ug;  // the window is contiguous (mirror rows)
-    constexpr int PF = PCS_NM_PF, NCH = (PCS_ABL & 2048) ? 1 : (NQ + PF - 1) / PF;  // window rows per chunk
+    constexpr int PF = PCS_NM_PF, NCH = (NQ + PF - 1) / PF;  // window rows per chunk
     G4<T> buf[2][PF];
 #pragma unroll
     for (int j = 0; j < PF; ++j)
@@ -432,7 +369,7 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
       if (c + 1 < NCH && ((c + 1) * PF) % 4 == 0) w4 = w4n;
     }
     const int wrow0 = s.row0 + a + 1 + 4 * wv;  // the wave's first global row
-    const bool vedge = PCS_NM_EDGE && (wrow0 < H || wrow0 + 3 >= n0 - H);  // rows of N_v near an image edge
+    const bool vedge = wrow0 < H || wrow0 + 3 >= n0 - H;  // rows of N_v near an image edge
     const bool top = gr >= 0 && gr < H, bot = gr >= n0 - H && gr < n0;
     const T* d = Wq + 64 + (top ? 8 * gr : 8 * H + 8 * (gr - (n0 - H)));
     const int kr0 = (wrow0 < H ? 0 : n0 - H) - s.row0;  // local row of the band's first image row
@@ -483,13 +420,12 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
       T* urow = U + slot * WU + 4 * ug;
       st4(urow, uo);
       bstore4<PCS_NM_SAUX>(rxn, (own ? (uint32_t)(lr + s.hx) * pitch : kOOB) + co_u, xo);
-#if PCS_NM_COOP65
       // the strip's 65th column c0 + 64 (never the image's last: n1 % 4 == 0), cooperatively: the wave's 4
       // outputs (its rows 4 wv + f, f = lane / 16) take 16 lanes each, lane fsub summing window taps
       // fsub and fsub + 16 (and edge term fsub), a row_ror DPP reduction inside the 16-lane row, then
       // every lane evaluates the update and lane fsub == 0 stores u (b65: the step's b at the column,
-      // loaded per lane with bv)
-      if (!(PCS_NMG_ABL & 4)) {
+      // loaded per lane with bv).  The last group's 4 lanes per wave in a serial 29-read branch lost to it.
+      {
         const int flr = a + 1 + fur, fgr = s.row0 + flr;
         const T* q0 = TR + M::tslot(flr - 2 * H) * WT + TW;  // the window is contiguous (mirror rows)
         T pg = T(0);
@@ -515,27 +451,6 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
         const bool frow = fgr < n0 && flr <= s.rows;
         if (fsub == 0) U[fslot * WU + TW] = (frow && c0 + TW < n1) ? reflect(xt, xe) : T(0);
       }
-#else
-      if (!(PCS_NMG_ABL & 4) && ug == GG - 1) {  // the strip's 65th column c0 + 64 (never the image's last: n1 % 4 == 0)
-        const T* q0 = p0 + 4;
-        T g4 = T(0);
-#pragma unroll
-        for (int q4 = 0; q4 < (NQ + 3) / 4; ++q4) {
-          const G4<T> w = lds4(Wq + 4 * q4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (4 * q4 + e < NQ) g4 += w.v[e] * lds1(q0 + (4 * q4 + e) * WT);
-        }
-        if (vedge) {
-#pragma unroll
-          for (int k = 0; k < H; ++k) g4 -= ((top || bot) ? d[k] : T(0)) * lds1(TR + (M::tslot(kr0) + k) * WT + TW);
-        }
-        const T xe = lds1(XR + (lr & 31) * WX + XL + TW);
-        const T xt = xt_of(g4 - b5, xe, lds1(Z0 + ui * WZ0 + TW), lds1(Z0 + (ui + 1) * WZ0 + TW), z1b.v[3],
-                           lds1(Z1 + (ui + 1) * WZ1 + TW + 4), false);
-        urow[4] = (rrow && ucg + 4 < n1) ? reflect(xt, xe) : T(0);
-      }
-#endif
     } else {  // backward / centred K: K^T z from z rows lr - 1 .. lr + 1, columns c - 1 .. c + 1
       const G4<T> xv4 = lds4(XR + (lr & 31) * WX + XL + 4 * ug);
       const T* z0p = Z0 + ui * WZ0 + 4 * ug + 4;  // tile row ui = row lr - 1, column c
@@ -550,8 +465,8 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
       // I: rows and columns >= 2 samples inside the image, no edge rules -- the same bits)
       // (intr: the row axis interior; intc: the column axis)
       auto xt_of = [&](auto intr, auto intc, T gd, T xv, const T (&w0)[5], const T (&w1)[5], int i1) {
-        constexpr bool I0 = decltype(intr)::value || (PCS_NMG_ABL & 2);
-        constexpr bool I1 = decltype(intc)::value || (PCS_NMG_ABL & 2);
+        constexpr bool I0 = decltype(intr)::value;
+        constexpr bool I1 = decltype(intc)::value;
         const T kt = pcs_fma(sw_d1_adj<KK, I0>(w0, gr, n0, edge), P.inv_step0,
                              sw_d1_adj<KK, I1>(w1, i1, n1, edge) * P.inv_step1);
         return primal_prox(grad_step(xv, gd, P), kt, gk, P);
@@ -574,7 +489,7 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
         }
       };
       if (rint && cint) items(std::true_type{}, std::true_type{});
-      else if (PCS_NMG_ROWFORM && rint) items(std::true_type{}, std::false_type{});
+      else if (rint) items(std::true_type{}, std::false_type{});
       else items(std::false_type{}, std::false_type{});
       if (own) {
         part[0] += (double)sdx;
@@ -589,7 +504,7 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
       // stores u.  Column c0 - 1 is >= H inside the image or outside it, c0 + 64 is < n1 - H or the
       // image's last group (no edge rows of N_h); every lane of the wave does useful work instead of
       // 8 lanes issuing a 29-read serial pass
-      if (!(PCS_NMG_ABL & 1)) {
+      {
         const int elr = a + 1 + eur, egr = s.row0 + elr;
         const T* q0 = TR + M::tslot(elr - 2 * H) * WT + ets;  // the window is contiguous (mirror rows)
         T part_g = T(0);
@@ -603,13 +518,7 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
           const T* ed = Wq + 64 + (etop ? 8 * egr : 8 * H + 8 * (egr - (n0 - H)));
           if (esub < H && (etop || ebot)) part_g -= ed[esub] * TR[(M::tslot(kr0) + esub) * WT + ets];
         }
-#if PCS_NMG_DPP
         part_g = oct_sum8(part_g);
-#else
-        part_g += __shfl_xor(part_g, 1, 64);
-        part_g += __shfl_xor(part_g, 2, 64);
-        part_g += __shfl_xor(part_g, 4, 64);
-#endif
         const T xe = XR[(elr & 31) * WX + XL + (ecol - c0)];
         const T w0[5] = {T(0), Z0[eur * WZ0 + eti], Z0[(eur + 1) * WZ0 + eti], Z0[(eur + 2) * WZ0 + eti], T(0)};
         const T* z1e = Z1 + (eur + 1) * WZ1 + eti;
@@ -683,8 +592,8 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
     G4<T> o0, o1;
     T sdz = T(0), sz = T(0);
     auto items = [&](auto intr, auto intc) {
-      constexpr bool I0 = decltype(intr)::value || (PCS_NMG_ABL & 2);
-      constexpr bool I1 = decltype(intc)::value || (PCS_NMG_ABL & 2);
+      constexpr bool I0 = decltype(intr)::value;
+      constexpr bool I1 = decltype(intc)::value;
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
         const T w0[5] = {T(0), uu.v[m], uc.v[m], ud.v[m], T(0)};
@@ -703,7 +612,7 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
       }
     };
     if (rint && cint) items(std::true_type{}, std::true_type{});
-    else if (PCS_NMG_ROWFORM && rint) items(std::true_type{}, std::false_type{});
+    else if (rint) items(std::true_type{}, std::false_type{});
     else items(std::false_type{}, std::false_type{});
     if (own) {
       part[2] += (double)sdz;
@@ -718,185 +627,16 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
     else p6f(a, ub);
   };
 
-  // ---- forward, PCS_NM_COLS: the column layout.  Lane `lane` of wave wv owns column cc = c0 + lane of
-  // the wave's rows: PV / update rows a + 1 + 4 wv + o, P6 rows a + 4 wv + o (o = 0..3).  PV reads the
-  // 4H + 4 window rows once each (b32, contiguous through the mirror) and feeds every row to the
-  // outputs it reaches; each output sums its taps in ascending order, as the row layout does
-  const int cc = c0 + lane;
-  const uint32_t co_cc = col_off(cc, n1);
-  const bool ccin = cc < n1, cclast = cc == n1 - 1;
-  auto pvc = [&](int a, const T (&bc)[4], T b5, int ub) {
-    const int lr0 = a + 1 + 4 * wv;
-    const T* p0 = TR + M::tslot(lr0 - 2 * H) * WT + lane;
-    constexpr int NR = NQ + 3, CH = 4, NCH = (NR + CH - 1) / CH;
-    static_assert(CH == 4, "chunk c's rows 4c .. 4c + 3 take taps of groups c - 1 and c");
-    T g[4] = {T(0), T(0), T(0), T(0)};
-    T buf[2][CH];
-    // taps 4 at a time (broadcast b128 reads, group c + 1 read one chunk ahead)
-    G4<T> wprev = {{T(0), T(0), T(0), T(0)}}, wcur = lds4(Wq), wnext;
-#pragma unroll
-    for (int j = 0; j < CH; ++j) buf[0][j] = lds1(p0 + j * WT);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      if (c + 1 < NCH) {
-#pragma unroll
-        for (int j = 0; j < CH; ++j)
-          if ((c + 1) * CH + j < NR) buf[(c + 1) & 1][j] = lds1(p0 + ((c + 1) * CH + j) * WT);
-        if (4 * (c + 1) < NQ) wnext = lds4(Wq + 4 * (c + 1));
-      }
-      pcs_fence();
-#pragma unroll
-      for (int j = 0; j < CH; ++j) {
-        const int q = c * CH + j;
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-          const int k = q - o;
-          if (q < NR && k >= 0 && k < NQ) {
-            const T w = k >= 4 * c ? wcur.v[k - 4 * c] : wprev.v[k - 4 * (c - 1)];
-            g[o] += w * buf[c & 1][j];
-          }
-        }
-      }
-#pragma unroll
-      for (int o = 0; o < 4; ++o) pin1(g[o]);
-      pcs_fence();
-      wprev = wcur;
-      if (c + 1 < NCH && 4 * (c + 1) < NQ) wcur = wnext;
-    }
-    const int wrow0 = s.row0 + lr0;  // the wave's first global row
-    const bool vedge = PCS_NM_EDGE && (wrow0 < H || wrow0 + 3 >= n0 - H);
-    const int kr0 = (wrow0 < H ? 0 : n0 - H) - s.row0;  // local row of the band's first image row
-    if (vedge) {  // exact rows of N_v near an image edge
-      T te[H];
-#pragma unroll
-      for (int k = 0; k < H; ++k) te[k] = lds1(TR + (M::tslot(kr0) + k) * WT + lane);  // contiguous (mirror)
-#pragma unroll
-      for (int o = 0; o < 4; ++o) {
-        const int gr = wrow0 + o;
-        const bool top = gr >= 0 && gr < H, bot = gr >= n0 - H && gr < n0;
-        const T* d = Wq + 64 + (top ? 8 * gr : bot ? 8 * H + 8 * (gr - (n0 - H)) : 0);
-#pragma unroll
-        for (int k = 0; k < H; ++k) g[o] -= ((top || bot) ? d[k] : T(0)) * te[k];
-      }
-    }
-    // update: z0 tile rows 4 wv .. 4 wv + 4 (row lr - 1 of output o at tile row 4 wv + o), z1 tile rows
-    // 4 wv + 1 + o at columns cc - 1 (index lane + 3) and cc (lane + 4)
-    T z0c[5];
-#pragma unroll
-    for (int o = 0; o < 5; ++o) z0c[o] = lds1(Z0 + (4 * wv + o) * WZ0 + lane);
-    T sdx = T(0), sx = T(0);
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-      const int lr = lr0 + o, gr = s.row0 + lr;
-      const T xv = lds1(XR + (lr & 31) * WX + XL + lane);
-      const T zl = lds1(Z1 + (4 * wv + 1 + o) * WZ1 + 3 + lane), zc = lds1(Z1 + (4 * wv + 1 + o) * WZ1 + 4 + lane);
-      const bool r_last = gr >= n0 - 1, r_first = gr <= 0;
-      const bool rrow = gr < n0 && lr <= s.rows;
-      const bool own = lr >= s0 && lr < s1 && gr < n0 && ccin;
-      T d0 = r_first ? T(0) : z0c[o];
-      if (!r_last) d0 -= z0c[o + 1];
-      const T d1 = zl - (cclast ? T(0) : zc);
-      const T xt = primal_prox(grad_step(xv, g[o] - bc[o], P), d0 * P.inv_step0 + d1 * P.inv_step1, gk, P);
-      int slot = 4 * wv + o + 1 + ub;
-      slot = slot >= UR ? slot - UR : slot;
-      U[slot * WU + lane] = (rrow && ccin) ? reflect(xt, xv) : T(0);
-      const T xnew = relax<false>(xt, xv, P);
-      bstore1<PCS_NM_SAUX>(rxn, (own ? (uint32_t)(lr + s.hx) * pitch : kOOB) + co_cc, xnew);
-      if (own) {
-        const T dx = xv - xnew;
-        sdx += dx * dx;
-        sx += xv * xv;
-      }
-    }
-    part[0] += (double)sdx;
-    part[1] += (double)sx;
-#if PCS_NM_COOP65
-    if (!(PCS_NMG_ABL & 4)) {  // the strip's 65th column, 16 lanes per output (as in pv)
-      const int flr = a + 1 + fur, fgr = s.row0 + flr;
-      const T* q0 = TR + M::tslot(flr - 2 * H) * WT + TW;
-      T pg = T(0);
-#pragma unroll
-      for (int j = 0; j < (NQ + 15) / 16; ++j) {
-        const int q = fsub + 16 * j;
-        if (q < NQ) pg += Wq[q] * q0[q * WT];
-      }
-      if (vedge) {
-        const bool ftop = fgr >= 0 && fgr < H, fbot = fgr >= n0 - H && fgr < n0;
-        const T* fd = Wq + 64 + (ftop ? 8 * fgr : fbot ? 8 * H + 8 * (fgr - (n0 - H)) : 0);
-        if (fsub < H && (ftop || fbot)) pg -= fd[fsub] * TR[(M::tslot(kr0) + fsub) * WT + TW];
-      }
-      pg = row_sum16(pg);
-      const T xe = XR[(flr & 31) * WX + XL + TW];
-      const bool f_last = fgr >= n0 - 1, f_first = fgr <= 0;
-      T d0 = f_first ? T(0) : Z0[fur * WZ0 + TW];
-      if (!f_last) d0 -= Z0[(fur + 1) * WZ0 + TW];
-      const T d1 = Z1[(fur + 1) * WZ1 + TW + 3] - Z1[(fur + 1) * WZ1 + TW + 4];
-      const T xt = primal_prox(grad_step(xe, pg - b5, P), d0 * P.inv_step0 + d1 * P.inv_step1, gk, P);
-      int fslot = fur + 1 + ub;
-      fslot = fslot >= UR ? fslot - UR : fslot;
-      const bool frow = fgr < n0 && flr <= s.rows;
-      if (fsub == 0) U[fslot * WU + TW] = (frow && c0 + TW < n1) ? reflect(xt, xe) : T(0);
-    }
-#else
-    static_assert(PCS_NM_COOP65 || !PCS_NM_COLS, "the column layout computes the 65th column cooperatively");
-#endif
-  };
-  // P6 in the column layout: z' on rows lr = a + 4 wv + o, column cc; u rows 4 wv + o .. 4 wv + 4 of the step
-  auto p6c = [&](int a, int ub) {
-    T uc[5];
-#pragma unroll
-    for (int o = 0; o < 5; ++o) {
-      int sl = 4 * wv + o + ub;
-      sl = sl >= 17 ? sl - 17 : sl;
-      uc[o] = lds1(U + sl * WU + lane);
-    }
-    T sdz = T(0), sz = T(0);
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-      const int lr = a + 4 * wv + o, gr = s.row0 + lr;
-      int sl = 4 * wv + o + ub;
-      sl = sl >= 17 ? sl - 17 : sl;
-      const T uright = lds1(U + sl * WU + lane + 1);
-      const T zv0 = lds1(Z0 + (4 * wv + o) * WZ0 + lane), zv1 = lds1(Z1 + (4 * wv + o) * WZ1 + 4 + lane);
-      const bool r_last = gr >= n0 - 1;
-      const bool own = lr >= s0 && lr < s1 && gr < n0 && ccin;
-      const T d0 = r_last ? T(0) : (uc[o + 1] - uc[o]);
-      const T d1 = cclast ? T(0) : (uright - uc[o]);
-      const T w[2] = {dual_arg(zv0, d0 * P.inv_step0, P), dual_arg(zv1, d1 * P.inv_step1, P)};
-      T zt[2];
-      fenchel_w<2, Fenchel::Direct, false>(HK, w, P, zt);
-      const T o0 = relax<false>(zt[0], zv0, P), o1 = relax<false>(zt[1], zv1, P);
-      const uint32_t off = (own ? (uint32_t)(lr + s.hz) * pitch : kOOB) + co_cc;
-      bstore1<PCS_NM_SAUX>(rzn0, off, o0);
-      bstore1<PCS_NM_SAUX>(rzn1, off, o1);
-      if (own) {
-        const T e0 = zv0 - o0, e1 = zv1 - o1;
-        sdz += e0 * e0 + e1 * e1;
-        sz += zv0 * zv0 + zv1 * zv1;
-      }
-    }
-    part[2] += (double)sdz;
-    part[3] += (double)sz;
-  };
-  constexpr bool COLS = !GEN && PCS_NM_COLS;
-  // b of the column layout: rows r0 + 4 wv + o, column cc
-  auto load_bc = [&](T (&bc)[4], int r0) {
-#pragma unroll
-    for (int o = 0; o < 4; ++o)
-      bc[o] = __uint_as_float(
-          __builtin_amdgcn_raw_buffer_load_b32(vb.r, (int)(vb.row_off(r0 + 4 * wv + o) + co_cc), 0, 0));
-  };
-
   // ================= prologue: t rows [s0 - 2H, s0 + 2H], u / x' on row s0 (GEN: t rows from s0 - 2H - 1,
   // u on rows s0 - 1 and s0)
   // b of a group = its 4 columns (bv) and, for the last group, the strip's 65th column (b5; GEN: the
   // lane's extra-column output, bm1)
   const uint32_t co_b5 = ug == GG - 1 ? col_off(c0 + TW, n1) : kOOB;
-  // forward, PCS_NM_COOP65: every lane loads b of its 65th-column output (row r0 + fur), else the last
-  // group's lanes b of their own row's 65th column
+  // forward: every lane loads b of its 65th-column output (row r0 + fur); GEN: the last group's lanes b of
+  // their own row's 65th column
   const uint32_t co_f65 = col_off(c0 + TW, n1);
   auto load_b5 = [&](int r0) -> T {
-    if constexpr (!GEN && PCS_NM_COOP65)
+    if constexpr (!GEN)
       return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(vb.r, (int)(vb.row_off(r0 + fur) + co_f65), 0, 0));
     else
       return bload4(vb.r, vb.row_off(r0 + ui) + co_b5).v[0];
@@ -904,7 +644,6 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
   constexpr int PR = GEN ? 1 : 0;  // extra prologue rows
   G4<T> xnx[KXN], bv;
   T b5, bm1 = T(0);
-  T bc[4];  // COLS: b of the lane's column on the wave's four update rows
   {
     G4<T> xv[KXP];
 #pragma unroll
@@ -921,10 +660,8 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
       b5 = bload4(vb.r, rbp + co_b5).v[0];
       bm1 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(vb.r, (int)(vb.row_off(s0 - TS + 1 + eur) + co_bx), 0, 0));
     } else {
-      if constexpr (COLS) load_bc(bc, s0 - TS + 1);  // wave 3: rows s0 - 3 .. s0
-      else bv = bload4(vb.r, (ui == TS - 1 ? vb.row_off(s0) : kOOB) + co_u);
-      if constexpr (PCS_NM_COOP65) b5 = load_b5(s0 - TS + 1);  // row s0: wave 3's last output row
-      else b5 = bload4(vb.r, (ui == TS - 1 ? vb.row_off(s0) : kOOB) + co_b5).v[0];
+      bv = bload4(vb.r, (ui == TS - 1 ? vb.row_off(s0) : kOOB) + co_u);
+      b5 = load_b5(s0 - TS + 1);  // row s0: wave 3's last output row
     }
 #pragma unroll
     for (int k = 0; k < KXP; ++k) {
@@ -933,9 +670,9 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
       const int r = e / GXL, g = e - (e / GXL) * GXL;
       st4(XR + ((s0 - 2 * H - PR + r) & 31) * WX + 4 * g, xv[k]);
     }
-#if PCS_NM_XEARLY
-    load_xn(xnx, s0 + 2 * H + 1);  // step 0's x rows: in flight with the prologue's (parked after PH)
-#endif
+    // step 0's x rows: in flight with the prologue's (parked after PH) -- one exposed load latency per segment, not
+    // two: C3 106.7-106.9 against 107.0-107.8 us loaded after the prologue's PV (profiles/r3_ck43_xe_*ab.txt)
+    load_xn(xnx, s0 + 2 * H + 1);
     vm_wait<0>();
   }
   if (stop_raw) return;  // loop already stopped (solver.py:65-66): loads landed, nothing stored
@@ -944,13 +681,7 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
   if (ui + TS < 4 * H + 1 + PR) ph(s0 - 2 * H - PR + TS + ui);  // t rows [.. + 16, s0 + 2H]
   lds_barrier();
   // u on row s0 (GEN: s0 - 1 too) -> the ring slots of step 0's rows a - 1, a; x' on row s0 (rows above: not own)
-  if (wv == 3) {
-    if constexpr (COLS) pvc(s0 - TS, bc, b5, UR - TS);
-    else pv(s0 - TS, bv, b5, bm1, UR - TS);
-  }
-#if !PCS_NM_XEARLY
-  load_xn(xnx, s0 + 2 * H + 1);        // step 0's x rows [s0 + 2H + 1, s0 + 2H + 17)
-#endif
+  if (wv == 3) pv(s0 - TS, bv, b5, bm1, UR - TS);
   lds_barrier();
   store_xn(xnx, s0 + 2 * H + 1);  // slots of rows [s0 + 2H - 31, s0 + 2H - 15): read by PH above only
 
@@ -962,10 +693,10 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
     lds_barrier();  // step k-1 done with U, Z and the t / x ring rows it read; its x rows landed
     asm volatile("" : "+v"(wz));
     Wq = W + wz;
-    // this step's z tiles (LDS-DMA) and b, the next step's x rows (registers, landed after P6)
-#if PCS_NM_PRIO
-    __builtin_amdgcn_s_setprio(3);  // the step's loads issue ahead of other waves' VALU
-#endif
+    // this step's z tiles (LDS-DMA) and b, the next step's x rows (registers, landed after P6); they issue at
+    // wave priority 3, ahead of other waves' VALU (0 again for the LDS / VALU phases): 113.1-113.6 against
+    // 115.9-116.5 us without (4 alternating reps)
+    __builtin_amdgcn_s_setprio(3);
     // The z tiles land through LDS-DMA loads; before the barrier that precedes their first read the wave
     // waits until only the loads it issued after them are outstanding.  Forward K: b (bv, b5) and the x
     // rows, counted.  GEN: its b values (bm1 of the extra-column lanes, b5 of the last group) are used on
@@ -973,39 +704,27 @@ __device__ __forceinline__ void nmarch_task(const T* __restrict__ x, T* __restri
     // they left the last tile load in flight when the tiles were read (a race: the C3 centred iterate
     // differed between runs from the second iteration on).  GEN therefore issues every load ahead of the
     // tiles and waits for all of them (tools/vmcnt_check.py checks the counts in the assembly).
-#ifndef PCS_NM_LOADFIRST  // diagnostics: the forward kernel with GEN's load order and full wait
-#define PCS_NM_LOADFIRST 0
-#endif
-    constexpr bool LF = GEN || (PCS_NM_LOADFIRST && !COLS);
-    if constexpr (LF) {
-      if constexpr (GEN) bm1 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(vb.r, (int)(vb.row_off(a + 1 + eur) + co_bx), 0, 0));
+    if constexpr (GEN) {
+      bm1 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(vb.r, (int)(vb.row_off(a + 1 + eur) + co_bx), 0, 0));
       bv = bload4a<PCS_NM_LAUX>(vb.r, vb.row_off(a + 1 + ui) + co_u);
       b5 = load_b5(a + 1);
       load_xn(xnx, a + 2 * H + 1 + TS);
       load_z(a, 0);
     } else {
       load_z(a, 0);
-      if constexpr (COLS) {
-        load_bc(bc, a + 1);
-      } else {
-        const uint32_t rb = vb.row_off(a + 1 + ui);
-        bv = bload4a<PCS_NM_LAUX>(vb.r, rb + co_u);
-      }
+      const uint32_t rb = vb.row_off(a + 1 + ui);
+      bv = bload4a<PCS_NM_LAUX>(vb.r, rb + co_u);
       b5 = load_b5(a + 1);
       load_xn(xnx, a + 2 * H + 1 + TS);
     }
-#if PCS_NM_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     ph(a + 2 * H + 1 + ui);
-    if constexpr (LF) vm_wait<0>();
-    else vm_wait<KXN + (COLS ? 5 : 2)>();  // this wave's z tile loads have landed (b and the x rows may be in flight)
+    if constexpr (GEN) vm_wait<0>();
+    else vm_wait<KXN + 2>();  // this wave's z tile loads have landed (b and the x rows may be in flight)
     lds_barrier();
-    if constexpr (COLS) pvc(a, bc, b5, ub);
-    else pv(a, bv, b5, bm1, ub);
+    pv(a, bv, b5, bm1, ub);
     lds_barrier();
-    if constexpr (COLS) p6c(a, ub);
-    else p6(a, ub);
+    p6(a, ub);
     store_xn(xnx, a + 2 * H + 1 + TS);  // x ring slots of rows [a + 2H - 15, a + 2H + 1): read above
     if constexpr (GEN) ub = ub + TS >= UR ? ub + TS - UR : ub + TS;
     else ub = ub == 0 ? 16 : ub - 1;
@@ -1029,15 +748,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PCS_NM_WPE))
   __shared__ double red[4 * (NT / 64)];
   __shared__ int flag[2];
   if (fin_slot(ro, ntasks, ctrl, hist, red, flag)) return;  // deferred finalization (pds_ctrl.hpp)
-  const int stop_raw = stop_flag_early(ctrl, ro);  // consumed in the task (PCS_DEFER_STOP)
+  const int stop_raw = stop_flag_early(ctrl, ro);  // consumed in the task
   const bool stopped = !stop_deferred(ro) && stop_requested(ctrl, ro, flag);
   if (stopped && ro.sums == nullptr) return;  // loop already stopped (solver.py:65-66)
 
-  int task;  // XCD-aware bijective remap: blocks b, b+8, ... share an XCD -> adjacent strips
-  {
-    const int bb = (int)blockIdx.x - fin_shift(ro), q = ntasks / 8, r = ntasks % 8, xcd = bb % 8, k = bb / 8;
-    task = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int task = xcd_task((int)blockIdx.x - fin_shift(ro), ntasks);  // XCD-aware (common.hpp)
   const int seg = task / tiles_x, strip = task - seg * tiles_x;
   int s0, s1;
   band_rows(bd, seg, s0, s1);
@@ -1045,7 +760,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PCS_NM_WPE))
 
   double part[4] = {0.0, 0.0, 0.0, 0.0};
   if (!stopped) {
-    if (PCS_NM_GKSPLIT && gk == PCS_G_NULL)  // uniform
+    // the G = 0 problem (the C3 benchmark's) runs a copy of the task compiled with that constant, so that prox_g's
+    // scalar branches on gk -- four per thread and step -- and the live gk / seg_a / seg_b leave its loop
+    if (gk == PCS_G_NULL)  // uniform
       nmarch_task<T, H, HK, NT, PCS_FORWARD>(x, xn, z, zn, b, tq, s, P, PCS_G_NULL, 0, s0, s1, c0, sm, zs0, zs1, part,
                                              stop_raw);
     else
@@ -1071,15 +788,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PCS_NM_WPE))
   __shared__ double red[4 * (NT / 64)];
   __shared__ int flag[2];
   if (fin_slot(ro, ntasks, ctrl, hist, red, flag)) return;  // deferred finalization (pds_ctrl.hpp)
-  const int stop_raw = stop_flag_early(ctrl, ro);  // consumed in the task (PCS_DEFER_STOP)
+  const int stop_raw = stop_flag_early(ctrl, ro);  // consumed in the task
   const bool stopped = !stop_deferred(ro) && stop_requested(ctrl, ro, flag);
   if (stopped && ro.sums == nullptr) return;  // loop already stopped (solver.py:65-66)
 
-  int task;  // XCD-aware bijective remap: blocks b, b+8, ... share an XCD -> adjacent strips
-  {
-    const int bb = (int)blockIdx.x - fin_shift(ro), q = ntasks / 8, r = ntasks % 8, xcd = bb % 8, k = bb / 8;
-    task = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int task = xcd_task((int)blockIdx.x - fin_shift(ro), ntasks);  // XCD-aware (common.hpp)
   const int seg = task / tiles_x, strip = task - seg * tiles_x;
   int s0, s1;
   band_rows(bd, seg, s0, s1);

@@ -19,11 +19,6 @@
 
 namespace pcs {
 
-// wave priority 3 while a step's loads issue (as pds_nmarch.hpp): C2 29.8-30.1 against
-// 30.2-30.4 us per iteration (3 alternating reps, tools/c2_ab.sh); PCS_PT_PRIO=0 drops it
-#ifndef PCS_PT_PRIO
-#define PCS_PT_PRIO 1
-#endif
 // cache-policy bits of the per-launch kernel's x' / z' stores (16 = sc1: written through, not left dirty in L2)
 // C2 2048^2: 31.4 against 32.3 us per iteration, C3 4096^2: 112.7 against 113.9 us (two alternating
 // reps each, profiles/r3_store_policy_ab.txt)
@@ -68,12 +63,9 @@ __device__ __forceinline__ void pt_task(const float* __restrict__ x, float* __re
   const int ui = 2 * hb + lgrp, ug = lidx;  // P45 / P6: row ui of the step, column group ug
   const int ucg = c0 + 4 * ug;
   // column c + 4 is kept by group 15 only: the other groups' fifth-column loads carry kOOB (no memory
-  // request; their fifth column is computed from zeros and dropped).  PCS_PT_E5=0: every group loads it
-#ifndef PCS_PT_E5
-#define PCS_PT_E5 1
-#endif
+  // request; their fifth column is computed from zeros and dropped)
   const uint32_t co_u = col_off(ucg, n1),
-                 co_e = (!PCS_PT_E5 || ug == TW / 4 - 1) ? col_off(ucg + 4, n1) : kOOB;
+                 co_e = ug == TW / 4 - 1 ? col_off(ucg + 4, n1) : kOOB;
   uint32_t co_z0[KZ0], co_z1[KZ1];
   int rr_z0[KZ0], rr_z1[KZ1];
   // bit 2: U group in; 3: U column c + 4 in; 4: U group is the last
@@ -226,22 +218,16 @@ __device__ __forceinline__ void pt_task(const float* __restrict__ x, float* __re
     const int fl = launder(flags);
     lds_barrier();  // previous P6 done with Z, U rows
     land_z();
-#if PCS_PT_PRIO
+    // wave priority 3 while a step's loads issue (as pds_nmarch.hpp): C2 29.8-30.1 against 30.2-30.4 us per
+    // iteration without (3 alternating reps, tools/c2_ab.sh)
     __builtin_amdgcn_s_setprio(3);
-#endif
     if (k + 1 < nsteps) loads_z(a + TS);  // next step's z flies during this step's P45 and P6
-#if PCS_PT_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     lds_barrier();
     p45(a, fl, ub);
-#if PCS_PT_PRIO
     __builtin_amdgcn_s_setprio(3);
-#endif
     if (k + 1 < nsteps) loads_x(a + TS);  // next step's x, y|g during this step's P6
-#if PCS_PT_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     lds_barrier();
     p6(a, fl, ub);
     ub = ub == 0 ? 16 : ub - 1;
@@ -262,11 +248,7 @@ __global__ __launch_bounds__(256) void k_pds2d_pt(const float* __restrict__ x, f
   if (fin_slot(ro, ntasks, ctrl, hist, red, flag)) return;  // deferred finalization (pds_ctrl.hpp)
   const bool stopped = stop_requested(ctrl, ro, flag);
   if (stopped && ro.sums == nullptr) return;  // loop already stopped (solver.py:65-66)
-  int task;
-  {  // XCD-aware bijective remap: blocks b, b+8, ... share an XCD -> adjacent strips of a segment
-    const int b = (int)blockIdx.x - fin_shift(ro), q = ntasks / 8, r = ntasks % 8, xcd = b % 8, k = b / 8;
-    task = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int task = xcd_task((int)blockIdx.x - fin_shift(ro), ntasks);  // XCD-aware (common.hpp)
   const int seg = task / tiles_x, strip = task - seg * tiles_x;
   int s0, s1;
   band_rows(bd, seg, s0, s1);

@@ -55,11 +55,6 @@ namespace pcs {
 #define PCS_SM_WPE 1
 #endif
 
-// wave priority 3 while a step's loads issue (as pds_pt.hpp); PCS_SM_PRIO=0 (diagnostics) drops it
-#ifndef PCS_SM_PRIO
-#define PCS_SM_PRIO 1
-#endif
-
 enum { SK_LAP = 3 };  // KK: PCS_FORWARD / PCS_BACKWARD / PCS_CENTERED (2 components) or the Laplacian (1)
 // FK beyond the public kinds: grad F = g - b with g = N x = Conv^T Conv x from a buffer (the in-plane
 // normal-operator kernel, pcs_conv2d_sep_ata_planes) and b = Conv^T y (formed once per problem);
@@ -164,11 +159,8 @@ __device__ __forceinline__ void smarch_task(const T* __restrict__ x, T* __restri
   const int lc = 4 + 4 * ug, lce = ug == 0 ? 3 : lc + 4;  // their ring columns
   const bool ext_st = ug == 0 || ug == TW / 4 - 1;   // fifth columns K u reads: c0 - 1, c0 + 64
   // only groups 0 and 15 keep their fifth column: the others' fifth-column loads carry kOOB (no memory
-  // request; computed from zeros, never stored).  PCS_SM_E5=0: every group loads it
-#ifndef PCS_SM_E5
-#define PCS_SM_E5 1
-#endif
-  const uint32_t co_c = col_off(c, n1, ES), co_e = (!PCS_SM_E5 || ext_st) ? col_off(ce, n1, ES) : kOOB;
+  // request; computed from zeros, never stored)
+  const uint32_t co_c = col_off(c, n1, ES), co_e = ext_st ? col_off(ce, n1, ES) : kOOB;
   // CI: the strip and its 4-column margins lie >= 2 columns inside the image (no column edge rule)
   const bool cin = CI || c < n1, ce_in = CI || (unsigned)ce < (unsigned)n1;
   uint32_t co_z[KZ];
@@ -402,12 +394,12 @@ __device__ __forceinline__ void smarch_task(const T* __restrict__ x, T* __restri
     const bool ri = s.row0 + a >= 2 && s.row0 + a + TS + 3 <= n0;
     lds_barrier();  // the previous step's Z phase is done with the rings
     land_z(a);
-    if (PCS_SM_PRIO) __builtin_amdgcn_s_setprio(3);  // the step's loads issue ahead of other waves' VALU
+    __builtin_amdgcn_s_setprio(3);  // the step's loads issue ahead of other waves' VALU (as pds_pt.hpp)
     if (k + 1 < nsteps) {
       loads_z(a + TS, -(1 << 30));
       loads_x(std::integral_constant<int, 1 - PB>{}, a + TS, -(1 << 30));
     }
-    if (PCS_SM_PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     lds_barrier();
     // U reads only the z ring; the Z rows read u rows up to their last row + 1 (+ 2 on the image's
     // first row only), all written by this step's U phase or earlier
@@ -438,14 +430,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PCS_SM_WPE)
   __shared__ double red[4 * 4];
   __shared__ int flag[2];
   if (fin_slot(ro, ntasks, ctrl, hist, red, flag)) return;  // deferred finalization (pds_ctrl.hpp)
-  const int stop_raw = stop_flag_early(ctrl, ro);  // consumed in the task (PCS_DEFER_STOP)
+  const int stop_raw = stop_flag_early(ctrl, ro);  // consumed in the task
   const bool stopped = !stop_deferred(ro) && stop_requested(ctrl, ro, flag);
   if (stopped && ro.sums == nullptr) return;  // loop already stopped (solver.py:65-66)
-  int task;
-  {  // XCD-aware bijective remap: blocks b, b+8, ... share an XCD -> adjacent strips of a segment
-    const int b = (int)blockIdx.x - fin_shift(ro), q = ntasks / 8, r = ntasks % 8, xcd = b % 8, k = b / 8;
-    task = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int task = xcd_task((int)blockIdx.x - fin_shift(ro), ntasks);  // XCD-aware (common.hpp)
   int strip, s0, s1;
   if (sp.nint < 0) {  // one segmentation for every strip
     const int seg = task / tiles_x;
@@ -463,10 +451,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PCS_SM_WPE)
   double part[4] = {0.0, 0.0, 0.0, 0.0};
   const int c0 = strip * SMarch<KK>::TW;
   if (!stopped) {
-#ifndef PCS_SM_ALLCI  // diagnostics (timing only, wrong border columns): every strip on the interior form
-#define PCS_SM_ALLCI 0
-#endif
-    if (PCS_SM_ALLCI || (c0 >= 4 && c0 + SMarch<KK>::TW + 6 <= s.n1))  // columns [c0 - 2, c0 + 66) >= 2 inside: no column edge rule
+    if (c0 >= 4 && c0 + SMarch<KK>::TW + 6 <= s.n1)  // columns [c0 - 2, c0 + 66) >= 2 inside: no column edge rule
       smarch_task<T, KK, FK, HK, true>(x, xn, z, zn, gsrc, bsrc, msrc, mdst, s, P, Q, gk, s0, s1, c0, sm, part,
                                            stop_raw);
     else

@@ -28,13 +28,6 @@
 #include "pds_ctrl.hpp"
 #include "pds_update.hpp"
 
-// Diagnostics only: bit k skips phase k (0 P1, 1 P2, 2 P3, 3 P4, 4 P5, 5 P6, 6 X->LDS,
-// 7 z->LDS) so rocprof counters can be attributed to phases.  Results are wrong.
-#ifndef PCS_ABLATE
-#define PCS_ABLATE 0
-#endif
-#define PCS_ON(bit) (!(PCS_ABLATE & (1 << (bit))))
-
 namespace pcs {
 
 template <int V>
@@ -228,7 +221,7 @@ __device__ __forceinline__ void pds2d_tile(const T* __restrict__ x, T* __restric
 #pragma unroll
     for (int k = 0; k < PX; ++k) {
       const int e = tid + k * NT;
-      if (PCS_ON(6) && e < HX * GX) st4(bufX + 4 * e, xr[k]);  // dense rows: pitch WX = 4 GX
+      if (e < HX * GX) st4(bufX + 4 * e, xr[k]);  // dense rows: pitch WX = 4 GX
     }
     __syncthreads();
   }
@@ -260,10 +253,10 @@ __device__ __forceinline__ void pds2d_tile(const T* __restrict__ x, T* __restric
 
   if constexpr (CONV) {
     // P1: A = forward row conv of X on the R columns                (bufX -> bufA)
-    if (PCS_ON(0)) row_pass<T, H, true, NT>(bufX, WX, bufA, WR, HX, GR, w1);
+    row_pass<T, H, true, NT>(bufX, WX, bufA, WR, HX, GR, w1);
     __syncthreads();
     // P2: R = forward col conv of A - y, zero outside the image      (bufA -> bufX)
-    if (PCS_ON(1) && p2_on) {
+    if (p2_on) {
       G4<T> acc[RR2];
       col_item<T, H, RR2, true>(bufA, WR, HX, p2_i0, p2_g, w0, acc);
 #pragma unroll
@@ -289,7 +282,7 @@ __device__ __forceinline__ void pds2d_tile(const T* __restrict__ x, T* __restric
     }
     __syncthreads();
     // P3: B = adjoint col pass of R: B[i] = sum_s w0[s] R[i + s]    (bufX -> bufA)
-    if (PCS_ON(2) && tid < cdiv(HG, RR3) * GR) {
+    if (tid < cdiv(HG, RR3) * GR) {
       const int i0 = (tid / GR) * RR3, g = tid - (tid / GR) * GR;
       G4<T> acc[RR3];
       col_item<T, H, RR3, false>(bufX, WR, HR, i0, g, w0, acc);
@@ -299,7 +292,7 @@ __device__ __forceinline__ void pds2d_tile(const T* __restrict__ x, T* __restric
     }
     __syncthreads();
     // P4: Gd = adjoint row pass of B on the U columns                (bufA -> bufX[0, SZ_U))
-    if (PCS_ON(3)) row_pass<T, H, false, NT>(bufA, WR, Gd, WG, HG, GG, w1);
+    row_pass<T, H, false, NT>(bufA, WR, Gd, WG, HG, GG, w1);
     __syncthreads();
   }
 
@@ -307,7 +300,6 @@ __device__ __forceinline__ void pds2d_tile(const T* __restrict__ x, T* __restric
 #pragma unroll
   for (int k = 0; k < PZ; ++k) {
     const int e = tid + k * NT;
-    if (!PCS_ON(7)) continue;
     if (e < NZ0) {
       st4(Z0 + 4 * e, zr[k]);  // dense, pitch WG
     } else if (e < NZ0 + NZ1) {
@@ -320,7 +312,7 @@ __device__ __forceinline__ void pds2d_tile(const T* __restrict__ x, T* __restric
 #pragma unroll
   for (int k = 0; k < PU; ++k) {
     const int e = tid + k * NT;
-    if (!PCS_ON(4) || e >= HG * GG) continue;
+    if (e >= HG * GG) continue;
     const int i = e / GG, g = e - i * GG;
     const int64_t lr = t0 + i, gr = s.row0 + lr;
     G4<T> gd;
@@ -384,7 +376,7 @@ __device__ __forceinline__ void pds2d_tile(const T* __restrict__ x, T* __restric
 #pragma unroll
   for (int k = 0; k < PD; ++k) {
     const int e = tid + k * NT;
-    if (!PCS_ON(5) || e >= TH * (TW / 4)) continue;
+    if (e >= TH * (TW / 4)) continue;
     const int i = e / (TW / 4), g = e - i * (TW / 4);
     const int64_t lr = t0 + i, gr = s.row0 + lr;
     if (!INT && (lr >= s.rows || gr >= n0)) continue;
@@ -469,12 +461,7 @@ __global__ __launch_bounds__(NT) void k_pds2d(const T* __restrict__ x, T* __rest
   const bool stopped = stop_requested(ctrl, ro, flag);
   if (stopped && ro.sums == nullptr) return;  // loop already stopped (solver.py:65-66)
 
-  // XCD-aware bijective remap: blocks b, b+8, ... share an XCD -> give them adjacent tiles.
-  int tile;
-  {
-    const int b = (int)blockIdx.x - fin_shift(ro), q = ntiles / 8, r = ntiles % 8, xcd = b % 8, k = b / 8;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int tile = xcd_task((int)blockIdx.x - fin_shift(ro), ntiles);  // XCD-aware (common.hpp)
   const int ty = tile / tiles_x, txs = tile - ty * tiles_x;
   const int tx = txs < bl ? txs : txs + tx_shift;  // strip subset: [0, bl) and the right-most strips
   const int64_t t0 = (int64_t)ty * TH, c0 = (int64_t)tx * TW;

@@ -38,12 +38,9 @@ struct AtaG {
   static_assert(RING >= RS + KT - 1, "ring holds the 14 rows above a step");
 };
 
-
+// rows per vertical item
 #ifndef PCS_ATA_RB
 #define PCS_ATA_RB 2
-#endif
-#ifndef PCS_ATA_HREG
-#define PCS_ATA_HREG 0
 #endif
 
 // one vertical 15-tap pass over a ring of rows: acc[r] = sum_t h(t) ring[(base + r0 + r - t) mod RING]
@@ -96,24 +93,8 @@ __global__ __launch_bounds__(AtaG::NT) void k_sep2d_ata(const T* __restrict__ in
     hv[t] = t < ka ? ha_[t] : T(0);
     hh[t] = (t >= padb && t - padb < kb) ? hb_[t - padb] : T(0);
   }
-#if PCS_ATA_HREG
-  T hreg[KT];  // horizontal taps in registers (P1 / P4 read each once per 4 outputs)
-#pragma unroll
-  for (int t = 0; t < KT; ++t) hreg[t] = (t >= padb && t - padb < kb) ? hb_[t - padb] : T(0);
-#define PCS_HH(t) hreg[t]
-#else
-#define PCS_HH(t) hh[t]
-#endif
-  int64_t t0, t_end, t_stride;
-  {  // XCD x owns a contiguous share of the task list; its blocks take consecutive tasks
-    const int64_t b = blockIdx.x, nb = gridDim.x, xcd = b % 8, k = b / 8, q = nb / 8, r = nb % 8;
-    const int64_t nbx = q + (xcd < r ? 1 : 0);
-    const int64_t before = xcd * q + (xcd < r ? xcd : r);
-    const int64_t lo = ntasks * before / nb, hi = ntasks * (before + nbx) / nb;
-    t0 = lo + k;
-    t_end = hi;
-    t_stride = nbx;
-  }
+  const XcdShare own = xcd_share(ntasks);  // XCD x owns a contiguous share of the task list (common.hpp)
+  const int64_t t0 = own.t0, t_end = own.end, t_stride = own.stride;
   if (t0 >= t_end) return;
   const int tid = threadIdx.x;
   struct Cur {
@@ -193,7 +174,7 @@ __global__ __launch_bounds__(AtaG::NT) void k_sep2d_ata(const T* __restrict__ in
         for (int m = 0; m < 4; ++m) {
           T acc = T(0);
 #pragma unroll
-          for (int t = 0; t < KT; ++t) acc += PCS_HH(t) * w[SH1 + m + (KT - 1 - t)];
+          for (int t = 0; t < KT; ++t) acc += hh[t] * w[SH1 + m + (KT - 1 - t)];
           o.v[m] = (unsigned)(col + m) < (unsigned)n2 ? acc : T(0);
         }
         int slot = base + r;
@@ -250,7 +231,7 @@ __global__ __launch_bounds__(AtaG::NT) void k_sep2d_ata(const T* __restrict__ in
           for (int m = 0; m < 4; ++m) {
             T acc = T(0);
 #pragma unroll
-            for (int s = 0; s < KT; ++s) acc += PCS_HH(s) * w[SH4 + m + s];
+            for (int s = 0; s < KT; ++s) acc += hh[s] * w[SH4 + m + s];
             o.v[m] = acc;
           }
           if (row >= cur.a && row < cur.b && gc < n2) stq(dst + (int64_t)row * n2 + gc, o);
@@ -260,7 +241,6 @@ __global__ __launch_bounds__(AtaG::NT) void k_sep2d_ata(const T* __restrict__ in
     if (!more) break;
     cur = nxt;
   }
-#undef PCS_HH
 }
 
 template <typename T>

@@ -273,16 +273,8 @@ __global__ __launch_bounds__(NrmF::NT, 3) void k_sep2d_nrm(const T* __restrict__
   const T* evh = tab + 120;
   const T* ehl = tab + 176;
   const T* ehh = tab + 232;
-  int64_t t0, t_end, t_stride;
-  {  // XCD x owns a contiguous share of the task list; its blocks take consecutive tasks
-    const int64_t b = blockIdx.x, nb = gridDim.x, xcd = b % 8, k = b / 8, q = nb / 8, r = nb % 8;
-    const int64_t nbx = q + (xcd < r ? 1 : 0);
-    const int64_t before = xcd * q + (xcd < r ? xcd : r);
-    const int64_t lo = ntasks * before / nb, hi = ntasks * (before + nbx) / nb;
-    t0 = lo + k;
-    t_end = hi;
-    t_stride = nbx;
-  }
+  const XcdShare own = xcd_share(ntasks);  // XCD x owns a contiguous share of the task list (common.hpp)
+  const int64_t t0 = own.t0, t_end = own.end, t_stride = own.stride;
   if (t0 >= t_end) {
     if constexpr (EP::kApgd) ep.finish();
     return;
@@ -616,16 +608,8 @@ __global__ __launch_bounds__(256, 2) void k_sep2d_nrmm(const T* __restrict__ in,
   const T* evh = tab + 120;
   const T* ehl = tab + 176;
   const T* ehh = tab + 232;
-  int64_t t0, t_end, t_stride;
-  {  // XCD x owns a contiguous share of the task list; its blocks take consecutive tasks
-    const int64_t b = blockIdx.x, nb = gridDim.x, xcd = b % 8, k = b / 8, q = nb / 8, r = nb % 8;
-    const int64_t nbx = q + (xcd < r ? 1 : 0);
-    const int64_t before = xcd * q + (xcd < r ? xcd : r);
-    const int64_t lo = ntasks * before / nb, hi = ntasks * (before + nbx) / nb;
-    t0 = lo + k;
-    t_end = hi;
-    t_stride = nbx;
-  }
+  const XcdShare own = xcd_share(ntasks);  // XCD x owns a contiguous share of the task list (common.hpp)
+  const int64_t t0 = own.t0, t_end = own.end, t_stride = own.stride;
   if (t0 >= t_end) {
     if constexpr (EP::kApgd) ep.finish();
     return;

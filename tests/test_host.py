@@ -454,3 +454,25 @@ def test_update_rule_stated_once():
     assert not found, found
     body = open(os.path.join(csrc, 'pds_update.hpp')).read()
     assert {'fast_rsqrt', 'clip1', 'prox_g'} <= set(names.findall(body))
+
+
+def test_compile_time_switches_are_listed():
+    """Every `#ifndef PCS_…` switch of csrc/ is a row of the table in DESIGN.md §4.0 and the table names no other;
+    none of the retired names listed below that table occurs in csrc/ or in the Makefile again."""
+    csrc = os.path.join(REPO, 'pycsou_amd', 'csrc')
+    texts = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))}
+    guarded = {m for t in texts.values() for m in re.findall(r'^\s*#\s*ifndef\s+(PCS_\w+)', t, re.M)}
+    design = open(os.path.join(REPO, 'DESIGN.md')).read()
+    section = design.split('### 4.0 Compile-time switches of the kernel sources', 1)[1]
+    table, retired_text = section.split('Retired switches.', 1)
+    listed = set(re.findall(r'^\| `(PCS_\w+)` \|', table, re.M))
+    assert len(listed) >= 20 and guarded == listed, (sorted(guarded - listed), sorted(listed - guarded))
+    retired_text = retired_text.split('\n\n', 2)[1]  # the list that follows the paragraph
+    retired = set(re.findall(r'`(PCS_\w+)(?:\(\))?`', retired_text)) | {'g_pcs_stamps', 'pcs_debug_stamps'}
+    assert len(retired) >= 35 and {'PCS_NM_COLS', 'PCS_ABL', 'PCS_STAMPS', 'PCS_MB'} <= retired, sorted(retired)
+    assert not retired & listed, sorted(retired & listed)
+    texts['Makefile'] = open(os.path.join(REPO, 'Makefile')).read()
+    names = re.compile(r'\b(' + '|'.join(sorted(retired)) + r')\b')
+    found = [(f, i + 1, m.group(1)) for f, t in texts.items()
+             for i, line in enumerate(t.split('\n')) for m in names.finditer(line)]
+    assert not found, found

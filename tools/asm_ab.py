@@ -1,4 +1,4 @@
-"""Compare the device assembly of the fused-step units of two source trees, kernel by kernel.
+"""Compare the device assembly of the kernel units of two source trees, kernel by kernel.
 
     python tools/asm_ab.py TREE_A TREE_B [--units pds,pds_nm,...] [--jobs N] [--keep DIR]
 
@@ -19,7 +19,7 @@ import subprocess
 import sys
 import tempfile
 
-UNITS = ['pds', 'pds_nm', 'pds_sm32', 'pds_sm64', 'pds_nm64', 'pds_gen', 'pds3d']
+UNITS = ['pds', 'pds_nm', 'pds_sm32', 'pds_sm64', 'pds_nm64', 'pds_gen', 'pds3d', 'corr2d', 'sep_ata', 'apgd2d', 'conv']
 FIELDS = ['.vgpr_count', '.agpr_count', '.sgpr_count', '.group_segment_fixed_size', '.private_segment_fixed_size',
           '.vgpr_spill_count', '.sgpr_spill_count', 'Occupancy']
 

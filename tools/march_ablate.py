@@ -1,12 +1,12 @@
-"""Time the C3 fused step (k_pds2d_march) in several builds of the engine, alternating builds so
+"""Time the C3 fused step in several builds of the engine, alternating builds so
 box drift hits all alike.  Diagnostics only (GPU box):
 
   python3 tools/march_ablate.py base=pycsou_amd/lib/libpycsou_hip.so v1=pycsou_amd/lib/var/v1/libpycsou_hip.so
 
 Each build runs in its own process (the library is loaded at import): 300 ms spin-up, then the
 isolated per-launch mean (HIP events around each of 100 launches) and the back-to-back rate
-(200 launches, one event pair).  Variants with ablated phases compute wrong iterates; only
-their timing is meaningful.
+(200 launches, one event pair).  The builds are variants of the numeric parameters
+(tools/build_var.sh NAME -DPCS_NM_WPE=...) or of a working tree.
 """
 import ctypes
 import os
