@@ -937,6 +937,56 @@ int pcs_cg_dot(int dtype, const void* p, const void* q, int64_t n, int64_t nb, d
 int pcs_cg_update(int dtype, void* x, void* r, const void* p, const void* q, int64_t n, int64_t nb, double eps2,
                   void* state, double* partials, void* ctrl, double* hist, hipStream_t stream);
 
+/* ---------------------------------------------------------------- eigenvalues: re-orthogonalised Lanczos steps */
+
+/* The vector work of one step of the thick-restart Lanczos behind LinearOperator.eigenvals / singularvals
+ * (pycsou/core/linop.py:208-219 -> scipy.sparse.linalg.eigsh / svds -> ARPACK) between two applications of the
+ * operator.  Everything is fp64.  V: m + 1 rows of n elements, row stride ldv >= n elements; at step s (0 <= s < m)
+ * rows 0..s are orthonormal and w (n contiguous elements, outside V) holds A V_s.  Classical Gram-Schmidt twice:
+ *   pcs_orth_dots    h[i] = <V_i, w> for i <= s,  h[s+1] = <w, w>        (w is read once per group of
+ *                    PCS_ORTH_GROUP rows)
+ *   pcs_orth_update  w -= sum_{i<=s} h_in[i] V_i in place (rows in the order 0..s, one fma each), then, in the
+ *                    same launch, h_out[i] = <V_i, w_new> for i <= s and h_out[s+1] = <w_new, w_new>.  Up to
+ *                    PCS_ORTH_REG_ROWS rows (s < 24) a thread keeps its elements of every row in registers
+ *                    between the two, so the basis is read once (instantiations of 8, 16 and 24 rows);
+ *                    above, the rows are read a second time, in groups of PCS_ORTH_GROUP.
+ *   one step         dots(h1), update(h1 -> h2), update(h2 -> h3); h3 is what is left after two passes
+ *   pcs_orth_commit  H[i][s] = H[s][i] = h1[i] + h2[i] for i <= s;  beta[s] = sqrt(h3[s+1]);
+ *                    omega[s] = max_{i<=s} |h3[i]| / beta[s];  row s + 1 of V = w / beta[s].
+ *                    Breakdown: if beta_s <= brk sqrt(h1[s+1]) (an invariant subspace or w = 0; the caller passes
+ *                    brk, 0 <= brk < inf) row s + 1 is written as zeros, beta[s] = omega[s] = 0 and `breakdown`
+ *                    keeps the first such s.  The steps after it then see w = 0 and break down the same way:
+ *                    no division by zero, every value finite, the first index kept.
+ * V and w are only read by dots; update writes w alone; commit writes row s + 1 of V and the state alone.
+ * Sums: per-workgroup partials, then a finalising launch adds a row's partials in a fixed order; no atomics, the
+ * bits depend on n, s and the access path alone (16-byte loads when V and w are 16-byte aligned and ldv is even,
+ * element-wise otherwise).  Grid: min(ceil(n / 512), PCS_ORTH_MAX_BLOCKS) workgroups of 256 threads over the
+ * columns, grid-stride; for dots times the row groups.
+ *
+ * h, h_in, h_out, h1..h3: s + 2 doubles each (m + 1 serve every step); h_in != h_out.
+ * partials: pcs_orth_nblocks(n, rows) doubles for rows >= s + 1 ([s + 2][workgroups]; pcs_orth_nblocks(n, m)
+ *           serves every step), 8-byte aligned; contents on entry: arbitrary.
+ * state:    pcs_orth_state_bytes(m) bytes = m m + 2 m + 1 doubles, 8-byte aligned: H (m x m, row-major), beta[m],
+ *           omega[m], breakdown (the index of the first step that broke down, as a double; -1: none).  Contents on
+ *           entry to pcs_orth_state_init: arbitrary (H, beta, omega = 0, breakdown = -1); pcs_orth_commit writes
+ *           row and column s of H (entries i <= s), beta[s], omega[s] and the breakdown index.
+ * PCS_EINVAL before any device call: null pointer, n < 0, s < 0, s >= m (commit), m < 1, ldv < n, w overlapping
+ * rows 0..s+1 of V, h_in == h_out, brk negative or not finite.  PCS_EUNSUPPORTED: m > PCS_ORTH_MAX_M (for dots and
+ * update: s >= PCS_ORTH_MAX_M).  The size functions return the same statuses (rows, m < 1: PCS_EINVAL). */
+#define PCS_ORTH_MAX_M 256
+#define PCS_ORTH_GROUP 8
+#define PCS_ORTH_REG_ROWS 24
+#define PCS_ORTH_MAX_BLOCKS 1024
+int64_t pcs_orth_state_bytes(int64_t m);
+int64_t pcs_orth_nblocks(int64_t n, int64_t rows);
+int pcs_orth_state_init(void* state, int64_t m, hipStream_t stream);
+int pcs_orth_dots(const double* V, int64_t ldv, int64_t s, const double* w, int64_t n, double* h, double* partials,
+                  hipStream_t stream);
+int pcs_orth_update(const double* V, int64_t ldv, int64_t s, double* w, int64_t n, const double* h_in, double* h_out,
+                    double* partials, hipStream_t stream);
+int pcs_orth_commit(double* V, int64_t ldv, int64_t s, int64_t m, const double* w, int64_t n, const double* h1,
+                    const double* h2, const double* h3, double brk, void* state, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,9 @@ PCS_MDM_RADIAL, PCS_MDM_ZONAL = 0, 1
 PCS_MDM_MAX_DIM, PCS_MDM_ROWS, PCS_MDM_SLAB, PCS_MDM_SMALL_ROWS, PCS_MDM_MAX_GROUPS = 4, 64, 256, 16, 1024
 # pcs_cg_*: most workgroups per system, systems per launch (grid y)
 PCS_CG_MAX_BLOCKS, PCS_CG_MAX_NB = 1024, 65535
+# pcs_orth_*: largest basis, rows per group of the dots, most workgroups over the columns and their tile
+PCS_ORTH_MAX_M, PCS_ORTH_GROUP, PCS_ORTH_MAX_BLOCKS, PCS_ORTH_TILE = 256, 8, 1024, 512
+PCS_ORTH_REG_ROWS = 24      # pcs_orth_update keeps up to this many rows in registers (kernels of 8, 16, 24 rows)
 PCS_F_NULL, PCS_F_DENOISE, PCS_F_SEPCONV, PCS_F_GRADBUF, PCS_F_CONV2D, PCS_F_CONV0 = 0, 1, 2, 3, 4, 5
 PCS_M_NONE, PCS_M_L1LOSS = 0, 1
 # pcs_pds2d_path: the kernel family of a fused 2-D step
@@ -260,6 +263,12 @@ _SIGS = {
     'pcs_cg_dir': (_c_int, [_c_int, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp]),
     'pcs_cg_dot': (_c_int, [_c_int, _vp, _vp, _c_i64, _c_i64, _c_dbl, _vp, _vp, _vp, _vp]),
     'pcs_cg_update': (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_dbl, _vp, _vp, _vp, _vp, _vp]),
+    'pcs_orth_state_bytes': (_c_i64, [_c_i64]),
+    'pcs_orth_nblocks': (_c_i64, [_c_i64, _c_i64]),
+    'pcs_orth_state_init': (_c_int, [_vp, _c_i64, _vp]),
+    'pcs_orth_dots': (_c_int, [_vp, _c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp]),
+    'pcs_orth_update': (_c_int, [_vp, _c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _vp]),
+    'pcs_orth_commit': (_c_int, [_vp, _c_i64, _c_i64, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_dbl, _vp, _vp]),
 }
 
 EXPORTS = tuple(_SIGS)
@@ -310,6 +319,13 @@ def check(rc, name):
     if rc != 0:
         raise HipError(f'{name} returned status {rc}')
     return rc
+
+
+def check_size(v, name):
+    """A size function's value, or HipError for its negative status."""
+    if v < 0:
+        raise HipError(f'{name} returned status {v}')
+    return v
 
 
 def ptr(t):

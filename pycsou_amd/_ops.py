@@ -1048,3 +1048,279 @@ def cg_normal(op, Y, eps, rtol=1e-5, atol=0.0, maxiter=None, x0=None, chunk=CG_C
     info = CGInfo(*(np.concatenate([getattr(p[2], f) for p in parts]) for f in ('rnorm', 'active', 'breakdown')),
                   parts[int(np.argmax([p[1] for p in parts]))][2].hist)
     return torch.cat([p[0] for p in parts]), max(p[1] for p in parts), info
+
+
+# ---------------------------------------------------------------- eigenvalues: thick-restart Lanczos with CGS2
+
+# pcs_orth_*: largest basis (m), rows per group of pcs_orth_dots, most workgroups over the columns, their tile
+ORTH_MAX_M, ORTH_GROUP, ORTH_MAX_BLOCKS, ORTH_TILE = L.PCS_ORTH_MAX_M, L.PCS_ORTH_GROUP, L.PCS_ORTH_MAX_BLOCKS, \
+    L.PCS_ORTH_TILE
+SPECTRAL_WHICH = ('LM', 'LA', 'SA', 'BE')
+_EPS = float(np.finfo(np.float64).eps)
+
+
+def orth_state(m, dev):
+    """The state of a basis of `m` vectors: H (m x m), beta[m], omega[m], the breakdown index -- m m + 2 m + 1
+    float64 at exactly pcs_orth_state_bytes(m) bytes."""
+    return torch.empty(int(L.check_size(L.gpu().pcs_orth_state_bytes(int(m)), 'pcs_orth_state_bytes')) // 8,
+                       dtype=torch.float64, device=dev)
+
+
+def orth_partials(n, rows, dev):
+    """The per-workgroup partial sums of a step against `rows` basis rows: pcs_orth_nblocks(n, rows) doubles."""
+    return torch.empty(int(L.check_size(L.gpu().pcs_orth_nblocks(int(n), int(rows)), 'pcs_orth_nblocks')),
+                       dtype=torch.float64, device=dev)
+
+
+def _orth_basis(name, V, w):
+    """(ldv, n) of a basis (rows, n) with unit column stride and the contiguous vector w, fp64 on one GPU."""
+    if V.dim() != 2 or w.dim() != 1 or V.dtype != torch.float64 or w.dtype != torch.float64 or not V.is_cuda \
+            or w.device != V.device or w.shape[0] != V.shape[1] or (V.shape[1] > 1 and V.stride(1) != 1) \
+            or not w.is_contiguous():
+        raise ValueError(f'{name}: V must be a (rows, n) float64 GPU tensor with unit column stride and w a '
+                         f'contiguous float64 vector of n elements on the same GPU')
+    return int(V.stride(0)) if V.shape[0] > 1 else max(int(V.stride(0)), int(V.shape[1])), int(V.shape[1])
+
+
+def orth_state_init(state, m):
+    L.check(L.gpu().pcs_orth_state_init(L.ptr(state), int(m), L.stream()), 'pcs_orth_state_init')
+
+
+def orth_dots(V, s, w, h, partials):
+    """``pcs_orth_dots``: h[i] = <V_i, w> for i <= s, h[s+1] = <w, w>."""
+    ldv, n = _orth_basis('orth_dots', V, w)
+    L.check(L.gpu().pcs_orth_dots(L.ptr(V), ldv, int(s), L.ptr(w), n, L.ptr(h), L.ptr(partials), L.stream()),
+            'pcs_orth_dots')
+
+
+def orth_update(V, s, w, h_in, h_out, partials):
+    """``pcs_orth_update``: w -= sum_i h_in[i] V_i, then h_out as ``orth_dots`` of the new w."""
+    ldv, n = _orth_basis('orth_update', V, w)
+    L.check(L.gpu().pcs_orth_update(L.ptr(V), ldv, int(s), L.ptr(w), n, L.ptr(h_in), L.ptr(h_out), L.ptr(partials),
+                                    L.stream()), 'pcs_orth_update')
+
+
+def orth_commit(V, s, m, w, h1, h2, h3, brk, state):
+    """``pcs_orth_commit``: column s of H, beta_s, omega_s, the breakdown index and row s + 1 of V."""
+    ldv, n = _orth_basis('orth_commit', V, w)
+    L.check(L.gpu().pcs_orth_commit(L.ptr(V), ldv, int(s), int(m), L.ptr(w), n, L.ptr(h1), L.ptr(h2), L.ptr(h3),
+                                    float(brk), L.ptr(state), L.stream()), 'pcs_orth_commit')
+
+
+class _OrthHip:
+    """Basis, step and restart of ``eigsh_restarted`` on the pcs_orth_* kernels."""
+
+    def __init__(self, n, m, dev):
+        self.n, self.m, self.dev = n, m, dev
+        ldv = n + (n & 1)                                      # even stride: every row starts 16-byte aligned
+        self.V = torch.zeros((m + 1, ldv), dtype=torch.float64, device=dev)[:, :n]
+        self.w = torch.empty(n, dtype=torch.float64, device=dev)
+        self.h = [torch.empty(m + 1, dtype=torch.float64, device=dev) for _ in range(3)]
+        self.partials = orth_partials(n, m, dev)
+        self.state, self.fill_state = orth_state(m, dev), orth_state(m, dev)
+        self.brk = 8.0 * _EPS * np.sqrt(n)
+
+    def begin(self):
+        orth_state_init(self.state, self.m)
+
+    def _step(self, s, state):
+        h1, h2, h3 = self.h
+        orth_dots(self.V, s, self.w, h1, self.partials)
+        orth_update(self.V, s, self.w, h1, h2, self.partials)
+        orth_update(self.V, s, self.w, h2, h3, self.partials)
+        orth_commit(self.V, s, self.m, self.w, h1, h2, h3, self.brk, state)
+
+    def step(self, s, w):
+        self.w.copy_(w.reshape(-1))
+        self._step(s, self.state)
+
+    def read(self):
+        m = self.m
+        st = self.state.cpu().numpy()
+        return st[:m * m].reshape(m, m), st[m * m:m * m + m], st[m * m + m:m * m + 2 * m], int(st[-1])
+
+    def fill(self, row, vec):
+        """Row `row` = `vec` orthogonalised twice against the rows before it and normalised (same kernels)."""
+        orth_state_init(self.fill_state, self.m)
+        self.w.copy_(vec)
+        self._step(row - 1, self.fill_state)
+        return int(self.fill_state[-1:].cpu().numpy()[0]) < 0
+
+    def rotate(self, Y):
+        keep = Y.shape[1]
+        Yd = torch.as_tensor(np.ascontiguousarray(Y.T)).to(self.dev)
+        self.V[:keep].copy_(torch.matmul(Yd, self.V[:self.m]))
+        self.V[keep].copy_(self.V[self.m])
+
+
+class _OrthTorch:
+    """The same steps with torch products on any device (the comparator of tools/bench_spectral.py and what the
+    CPU test tier runs); no host synchronisation inside a step either."""
+
+    def __init__(self, n, m, dev):
+        self.n, self.m, self.dev = n, m, dev
+        f = dict(dtype=torch.float64, device=dev)
+        self.V = torch.zeros((m + 1, n), **f)
+        self.H, self.beta, self.omega = torch.zeros((m, m), **f), torch.zeros(m, **f), torch.zeros(m, **f)
+        self.broke_at = torch.full((), -1.0, **f)
+        self.brk = 8.0 * _EPS * np.sqrt(n)
+
+    def begin(self):
+        self.H.zero_()
+        self.beta.zero_()
+        self.omega.zero_()
+        self.broke_at.fill_(-1.0)
+
+    def _cgs2(self, s, w):
+        Vs = self.V[:s + 1]
+        h1 = torch.mv(Vs, w)
+        before = torch.dot(w, w)
+        w = w - torch.mv(Vs.t(), h1)
+        h2 = torch.mv(Vs, w)
+        w = w - torch.mv(Vs.t(), h2)
+        h3 = torch.mv(Vs, w)
+        b = torch.sqrt(torch.dot(w, w))
+        broke = b <= self.brk * torch.sqrt(before)
+        zero = torch.zeros_like(b)
+        self.V[s + 1] = torch.where(broke, torch.zeros_like(w), w / b)
+        return h1 + h2, torch.where(broke, zero, b), torch.where(broke, zero, h3.abs().max() / b), broke
+
+    def step(self, s, w):
+        c, b, om, broke = self._cgs2(s, w.reshape(-1).to(torch.float64))
+        self.H[:s + 1, s] = c
+        self.H[s, :s + 1] = c
+        self.beta[s], self.omega[s] = b, om
+        first = broke & (self.broke_at < 0)
+        self.broke_at.copy_(torch.where(first, torch.full_like(self.broke_at, float(s)), self.broke_at))
+
+    def read(self):
+        return self.H.cpu().numpy().copy(), self.beta.cpu().numpy().copy(), self.omega.cpu().numpy().copy(), \
+            int(self.broke_at.item())
+
+    def fill(self, row, vec):
+        return not bool(self._cgs2(row - 1, vec.clone())[3].item())
+
+    def rotate(self, Y):
+        keep = Y.shape[1]
+        Yd = torch.as_tensor(np.ascontiguousarray(Y.T)).to(self.dev)
+        self.V[:keep] = torch.matmul(Yd, self.V[:self.m])
+        self.V[keep] = self.V[self.m]
+
+
+def spectral_select(theta, k, which):
+    """Indices (ascending) of the `k` wanted values of the ascending array `theta`: 'LA' the largest, 'SA' the
+    smallest, 'LM' the largest in magnitude, 'BE' k // 2 from the low end and the rest from the high end."""
+    m = len(theta)
+    if which == 'LA':
+        idx = np.arange(m - k, m)
+    elif which == 'SA':
+        idx = np.arange(k)
+    elif which == 'LM':
+        idx = np.argsort(np.abs(theta), kind='stable')[m - k:]
+    elif which == 'BE':
+        idx = np.concatenate([np.arange(k // 2), np.arange(m - (k - k // 2), m)])
+    else:
+        raise ValueError(f"which must be one of {SPECTRAL_WHICH}, got {which!r}")
+    return np.sort(idx)
+
+
+def spectral_ncv(n, k, ncv=None):
+    """The basis size: ``ncv``, or ARPACK's default min(n, max(2 k + 1, 20))."""
+    return int(ncv) if ncv is not None else min(int(n), max(2 * int(k) + 1, 20))
+
+
+def eigsh_restarted(apply, n, k, which='LM', ncv=None, tol=0, maxiter=None, v0=None, device=None, orth='hip'):
+    """``k`` eigenvalues of the symmetric operator ``apply`` (fp64 device vector of ``n`` in, the same out) by
+    thick-restart Lanczos (Wu & Simon 2000) with full CGS2 re-orthogonalisation against a stored basis of
+    ``m = ncv`` (default min(n, max(2 k + 1, 20))) fp64 vectors; what ``scipy.sparse.linalg.eigsh`` computes with
+    ``return_eigenvectors=False``: an ascending fp64 NumPy array.
+
+    One cycle runs the steps j0..m-1 with no host synchronisation (``orth='hip'``: the pcs_orth_* kernels;
+    ``orth='torch'``: torch products, on any device).  Then H = V^T A V and the step scalars come to the host once,
+    ``eigh(H)`` gives the Ritz pairs (theta_i, y_i) and |beta_{m-1} y_i[m-1]| their residuals.  Pair i has
+    converged when its residual is at most max(tol_eff max(eps^(2/3), |theta_i|), 8 eps max |theta|), tol_eff =
+    ``tol`` or eps: ARPACK's criterion and a round-off floor.  Until the ``k`` wanted pairs have, the basis is
+    rotated onto keep = min(k + min(nconv, (m - k) // 2), m - 1) Ritz vectors (one matmul), H = diag(theta), row
+    ``keep`` becomes the last Lanczos vector and the next step's Gram-Schmidt coefficients are the coupling row.
+    A breakdown (an invariant subspace, a zero operator) fills the next row with a seeded random vector,
+    orthogonalised twice by the same step and normalised, and resumes there: the coupling is zero, and the rest of
+    a multiple eigenvalue is found this way.  ``maxiter``: restarts, default 10 n; then
+    ``scipy.sparse.linalg.ArpackNoConvergence`` with the converged values.  ``v0``: start vector (default: seeded).
+    """
+    n, k = int(n), int(k)
+    if which not in SPECTRAL_WHICH:
+        raise ValueError(f"which must be one of {SPECTRAL_WHICH}, got {which!r}")
+    if not 0 < k < n:
+        raise ValueError(f'k must satisfy 0 < k < n = {n}, got {k}')
+    m = spectral_ncv(n, k, ncv)
+    if not k < m <= n:
+        raise ValueError(f'ncv must satisfy k < ncv <= n, got ncv = {m} for k = {k}, n = {n}')
+    if orth not in ('hip', 'torch'):
+        raise ValueError(f"orth must be 'hip' or 'torch', got {orth!r}")
+    if orth == 'hip' and m > ORTH_MAX_M:
+        raise ValueError(f'the device basis holds at most {ORTH_MAX_M} vectors, got ncv = {m}')
+    dev = torch.device(device) if device is not None else device_of_orth(orth)
+    be = (_OrthHip if orth == 'hip' else _OrthTorch)(n, m, dev)
+    gen = torch.Generator(device=dev).manual_seed(0)    # on the device: no host vector of n, the same bits every run
+    if v0 is None:
+        q = torch.randn(n, generator=gen, dtype=torch.float64, device=dev)
+    else:
+        q = v0.detach() if isinstance(v0, torch.Tensor) else torch.as_tensor(np.asarray(v0, dtype=np.float64))
+        q = q.to(device=dev, dtype=torch.float64).reshape(-1)
+        if q.numel() != n:
+            raise ValueError(f'v0 must have {n} elements, got {q.numel()}')
+    nrm = float(torch.linalg.vector_norm(q))
+    if not (nrm > 0 and np.isfinite(nrm)):
+        raise ValueError('v0 must be a nonzero finite vector')
+    be.V[0] = q / nrm
+    tol_eff = float(tol) if tol else _EPS
+    maxiter = 10 * n if maxiter is None else int(maxiter)
+    H = np.zeros((m, m))
+    betas = np.zeros(m)
+    j0, restarts = 0, 0
+    while True:
+        j = j0
+        while True:                                     # one cycle; a breakdown resumes it one row further
+            be.begin()
+            for s in range(j, m):
+                be.step(s, apply(be.V[s]))
+            Hs, beta, _, broke_at = be.read()
+            end = m if broke_at < 0 else broke_at + 1
+            for s in range(j, end):
+                H[:s + 1, s] = Hs[:s + 1, s]
+                H[s, :s + 1] = Hs[s, :s + 1]
+            betas[j:end] = beta[j:end]
+            if broke_at < 0 or broke_at == m - 1:
+                break
+            j = broke_at + 1
+            if not be.fill(j, torch.randn(n, generator=gen, dtype=torch.float64, device=dev)):
+                raise RuntimeError('eigsh_restarted: a random vector fell into the span of the basis')
+        if not np.all(np.isfinite(H)):
+            raise ValueError('eigsh_restarted: the operator returned values that are not finite')
+        theta, Y = np.linalg.eigh(H)
+        res = np.abs(betas[m - 1] * Y[m - 1])
+        bar = np.maximum(tol_eff * np.maximum(_EPS ** (2.0 / 3.0), np.abs(theta)), 8.0 * _EPS * np.abs(theta).max())
+        conv = res <= bar
+        want = spectral_select(theta, k, which)
+        nconv = int(conv[want].sum())
+        if nconv == k:
+            return theta[want].copy()
+        if restarts >= maxiter:
+            from scipy.sparse.linalg import ArpackNoConvergence
+            raise ArpackNoConvergence(f'eigsh_restarted: {nconv} of {k} eigenvalues converged in {restarts} '
+                                      f'restarts', theta[want][conv[want]].copy(), None)
+        keep = min(k + min(nconv, (m - k) // 2), m - 1)
+        idx = spectral_select(theta, keep, which)
+        be.rotate(Y[:, idx])
+        H[:] = 0.0
+        H[np.arange(keep), np.arange(keep)] = theta[idx]
+        j0, restarts = keep, restarts + 1
+
+
+def device_of_orth(orth):
+    """The default device of ``eigsh_restarted``: the current GPU ('hip' has no other; 'torch' takes the CPU
+    when no GPU is visible)."""
+    if orth == 'torch' and not torch.cuda.is_available():
+        return torch.device('cpu')
+    L.gpu()
+    return device()

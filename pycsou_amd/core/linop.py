@@ -11,6 +11,11 @@ host loop of tens to hundreds of operator applications) by a device Lanczos iter
 on ``K^T K`` in O(1) vectors: every operator application and the recurrence stay on the
 GPU, only the small tridiagonal eigenproblem runs on the host every few steps.
 
+``eigenvals`` / ``singularvals`` (``linop.py:208-219``) replace ARPACK ``eigsh`` / ``svds`` on ``SciOp`` by a
+thick-restart Lanczos whose basis, re-orthogonalisation (``csrc/orth.hip``) and operator applications stay on the
+device (``_ops.eigsh_restarted``); what it does not serve -- ``which='SM'`` of ``eigenvals``, non-symmetric
+operators, other keyword arguments -- still goes to SciPy.
+
 ``pinv`` / ``PinvOp`` / ``dagger`` / ``LinOpPinv`` (``linop.py:397-440, 618-629``) replace PyLops'
 ``NormalEquationsInversion`` (SciPy ``cg`` on the normal equations) by batched conjugate gradients on the device
 (``_ops.cg_normal``, ``csrc/cg.hip``); ``todense`` / ``tosparse`` / ``cond`` (``linop.py:323-395``) go through the
@@ -205,9 +210,34 @@ class LinearOperator(DifferentiableMap):
     def SciOp(self):
         return self.tosciop()
 
+    _SPECTRAL_KW = ('tol', 'ncv', 'maxiter', 'v0')
+
+    def _device_spectral(self, n, k, kwargs, vectors_kw):
+        """The keyword arguments of ``_ops.eigsh_restarted`` when the device Lanczos serves this call, else None
+        (SciPy's path): only ``tol``, ``ncv``, ``maxiter``, ``v0`` and a false ``vectors_kw`` are understood, and
+        the basis must fit the kernels' limit."""
+        if any(key not in self._SPECTRAL_KW + (vectors_kw,) for key in kwargs) or kwargs.get(vectors_kw, False):
+            return None
+        kw = {key: kwargs[key] for key in self._SPECTRAL_KW if key in kwargs}
+        if isinstance(k, (int, np.integer)) and O.spectral_ncv(n, max(int(k), 0), kw.get('ncv')) > O.ORTH_MAX_M:
+            return None
+        return kw
+
     def eigenvals(self, k, which='LM', **kwargs):
+        """``linop.py:208-213``.  A symmetric operator with ``which`` in LM / LA / SA / BE runs the thick-restart
+        Lanczos on the device (``_ops.eigsh_restarted``: ``tol``, ``ncv``, ``maxiter`` and ``v0`` as ``eigsh``
+        takes them, ascending values back); ``which='SM'`` (no shift-invert on the device), any other keyword
+        argument, ``ncv`` above 256 and non-symmetric operators (complex eigenvalues) take SciPy's ARPACK wrappers
+        through ``SciOp``."""
         import scipy.sparse.linalg as spls
         if self.is_symmetric:
+            kw = self._device_spectral(self.shape[1], k, kwargs, 'return_eigenvectors') \
+                if which in O.SPECTRAL_WHICH else None
+            if kw is not None:
+                n, cdt = self.shape[1], self._compute_dtype()
+                if not 0 < k < n:
+                    raise ValueError(f'k must satisfy 0 < k < {n}, got k = {k}')
+                return O.eigsh_restarted(lambda v: self._apply(v.to(cdt)).to(torch.float64), n, k, which, **kw)
             return spls.eigsh(A=self.SciOp, k=k, which=which, return_eigenvectors=False, **kwargs)
         if self.is_square:
             return spls.eigs(A=self.SciOp, k=k, which=which, return_eigenvectors=False, **kwargs)
@@ -215,8 +245,24 @@ class LinearOperator(DifferentiableMap):
                                   'operators, use the method singularvals.')
 
     def singularvals(self, k, which='LM', **kwargs):
+        """``linop.py:215-219``.  ``which`` LM / SM: the device Lanczos on the smaller Gram operator (A^T A or
+        A A^T, as ``svds`` does), LA / SA there, and the roots of its eigenvalues, ascending; ``tol`` is that of
+        the Gram eigenproblem.  Other keyword arguments than ``tol``, ``ncv``, ``maxiter``, ``v0``: SciPy's
+        ``svds`` through ``SciOp``."""
         import scipy.sparse.linalg as spls
-        return spls.svds(A=self.SciOp, k=k, which=which, return_singular_vectors=False, **kwargs)
+        kw = self._device_spectral(min(self.shape), k, kwargs, 'return_singular_vectors') \
+            if which in ('LM', 'SM') else None
+        if kw is None:
+            return spls.svds(A=self.SciOp, k=k, which=which, return_singular_vectors=False, **kwargs)
+        n, cdt = min(self.shape), self._compute_dtype()
+        if not 1 <= k < n:
+            raise ValueError(f'k must satisfy 1 <= k < min(shape) = {n}, got k = {k}')
+        if self.shape[0] >= self.shape[1]:
+            gram = lambda v: self._adj(self._apply(v.to(cdt))).to(torch.float64)    # noqa: E731
+        else:
+            gram = lambda v: self._apply(self._adj(v.to(cdt))).to(torch.float64)    # noqa: E731
+        theta = O.eigsh_restarted(gram, n, k, 'LA' if which == 'LM' else 'SA', **kw)
+        return np.sqrt(np.maximum(theta, 0.0))
 
     def compute_lipschitz_cst(self, tol=1e-9, max_steps=5000, **kwargs):
         """Operator norm ``||K||_2`` (``pycsou/core/linop.py:279-321``: ARPACK ``svds`` / ``eigsh``
